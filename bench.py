@@ -14,6 +14,11 @@ One step = one pass over all of a rank's contigs with the bases and the window t
 ranks gather their logits to rank 0 over RCCL inside the timed region.  ``--gpus N`` without a torchrun
 environment starts N ranks itself (fresh child processes, created before this process touches the GPU).
 
+A plain run sets up, warms up, times ``--steps`` steps and prints the headline.  ``--full`` adds everything else the
+line can carry: the box calibration, the exact-f32 side measurement, the end-to-end FASTA -> TSV leg, the other configs
+as ``also`` and the CPU baseline (each can still be dropped with its ``--no-*`` switch).  ``--dump-outputs DIR`` writes
+the arrays the timed path returned in its last step as ``DIR/<name>.npy``.
+
 Prints ONE JSON line on rank 0 (see README / the driver contract).
 """
 
@@ -35,6 +40,8 @@ sys.path.insert(0, str(ROOT))
 F32_MFMA_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md chip table: v_mfma_f32_32x32x2_f32
 F16_MFMA_PEAK_TFLOPS = 2500.0     # dense f16/bf16 MFMA peak (same table); split-f16 issues 3 MFMAs/product
 HBM_PEAK_GBS = 8000.0
+DUMP_MAX_BYTES = 64 << 20         # --dump-outputs: above this the arrays are cut to the same seeded sample of rows
+DUMP_SAMPLE_SEED = 20261016
 
 CONFIGS = {
     "default": dict(model="brain", fsize=1500, contigs=10_000, seed=20260923, exact=None,
@@ -275,6 +282,25 @@ def e2e_leg(cfg, weights, wl, fsize, records: int = 0, seed: int | None = None):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def dump_outputs(out_dir, arrays: dict, max_bytes: int = DUMP_MAX_BYTES) -> None:
+    """Write ``arrays`` (name -> 2-D array, one row per window, all with the same row count) as ``out_dir/<name>.npy`` in
+    float32.  When they would exceed ``max_bytes`` together, every array keeps the same fixed, seeded sample of rows (in
+    window order) and ``row_index.npy`` (float64) names the windows kept."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    n_rows = next(iter(arrays.values())).shape[0] if arrays else 0
+    row_bytes = sum(v[:1].nbytes for v in arrays.values())
+    if n_rows and row_bytes * n_rows > max_bytes:
+        keep = max(1, max_bytes // (row_bytes + 8))        # (+ 8: the row's entry in row_index.npy)
+        rng = np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED))
+        idx = np.sort(rng.choice(n_rows, size=min(keep, n_rows), replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        np.save(out / "row_index.npy", idx.astype(np.float64))
+    for name, v in arrays.items():
+        np.save(out / f"{name}.npy", v)
+
+
 def pmc_fields(name: str, mode: str, fsize: int, chunk: int, avg_launch_ms: float):
     """HBM traffic and matrix-core utilisation of the dominant kernel from the committed rocprofv3 --pmc summaries
     (profiles/pmc_traffic.json, profiles/mfma_util.json) - attached only when they were collected on THIS kernel build."""
@@ -382,12 +408,21 @@ def main():
     ap.add_argument("--fsize", type=int, default=None)
     ap.add_argument("--chunk", type=int, default=0)
     ap.add_argument("--precision", choices=["f32", "f16x3"], default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-exact-f32", action="store_true", help="skip the short exact-f32 side measurement")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end FASTA -> TSV leg")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: box calibration, exact-f32 side measurement, "
+                         "end-to-end leg, the other configs (`also`) and the CPU baseline (each can be dropped with its "
+                         "--no-* switch); without it a run times its steps and prints the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step (prediction, reliability, G/C/A/T counts "
+                         "per window; with N ranks the gathered prediction) as DIR/<name>.npy in float32, at most 64 MB "
+                         "in all (a seeded sample of rows beyond that, named by row_index.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-exact-f32", action="store_true", help="--full: skip the short exact-f32 side measurement")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the end-to-end FASTA -> TSV leg")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the other BASELINE configs (`also`: frag1m and baseline500 at 2 timed steps each)")
-    ap.add_argument("--no-box", action="store_true", help="skip the box calibration (bare MFMA loop behind the timed steps)")
+                    help="--full: skip the other BASELINE configs (`also`: frag1m and baseline500 at 2 timed steps each)")
+    ap.add_argument("--no-box", action="store_true",
+                    help="--full: skip the box calibration (bare MFMA loop behind the timed steps)")
     ap.add_argument("--box-seconds", type=float, default=0.5)
     ap.add_argument("--no-profile", action="store_true",
                     help="experiments only: no HIP events around the conv launches (roofline fields read 0)")
@@ -418,6 +453,8 @@ def main():
                     help="experiments only (libjaeger_hip_exp.so): set the conv kernel's JG_DBG ablation mask after "
                          "the warm-up steps (the timed steps then read real activations; their results are wrong)")
     args = ap.parse_args()
+    if not args.full:                   # a plain run: the headline's steps and nothing else
+        args.no_cpu_baseline = args.no_exact_f32 = args.no_e2e = args.no_also = args.no_box = True
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
@@ -601,6 +638,16 @@ def measure(args, name: str, steps: int, warmup: int, ctx: dict, headline: bool)
     if rank == 0 and args.dump_gather and headline:
         parts = [g.cpu().numpy() for g in gathered] if gathered is not None else [d_pred.cpu().numpy()]
         np.save(args.dump_gather, np.concatenate(parts, axis=0))
+    if rank == 0 and args.dump_outputs and headline:
+        # the last timed step's results, before the exact-f32 side measurement overwrites the first windows' rows
+        if world > 1 and gathered is not None:
+            outs = {"prediction": np.concatenate([g.cpu().numpy() for g in gathered], axis=0)}
+        else:
+            outs = {"prediction": d_pred.cpu().numpy()}
+            if n_rel:
+                outs["reliability"] = d_rel.cpu().numpy()
+            outs["counts"] = d_counts.cpu().numpy()
+        dump_outputs(args.dump_outputs, outs)
     line = None
     if rank == 0:
         n_steps = max(steps, 1)

@@ -9,7 +9,7 @@ G2="GRBM_GUI_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK
 i=0
 for grp in "$G1" "$G2"; do
   i=$((i+1))
-  timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/g$i -- python3 $R/bench.py --contigs 400 --steps 1 --warmup 1 --precision f32 --no-cpu-baseline --no-exact-f32 --no-e2e > $O/g$i.json 2> $O/g$i.err
+  timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/g$i -- python3 $R/bench.py --full --contigs 400 --steps 1 --warmup 1 --precision f32 --no-cpu-baseline --no-exact-f32 --no-e2e > $O/g$i.json 2> $O/g$i.err
 done
 python3 - <<PY
 import csv, glob, collections

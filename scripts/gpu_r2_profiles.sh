@@ -4,14 +4,14 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r2p
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cp $O/prof_default/*/*kernel_stats.csv $O/default_kernel_stats.csv
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_small -- python3 $R/bench.py --config baseline500 > $O/bench_baseline500.json 2> $O/bench_baseline500.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_small -- python3 $R/bench.py --full --config baseline500 > $O/bench_baseline500.json 2> $O/bench_baseline500.err
 cp $O/prof_small/*/*kernel_stats.csv $O/baseline500_kernel_stats.csv
 for cfg in default baseline500; do
   n=1000; [ $cfg = baseline500 ] && n=200000
   for grp in FETCH_SIZE WRITE_SIZE; do
-    rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/pmc_${cfg}_$grp -- python3 $R/bench.py --config $cfg --contigs $n --steps 1 --warmup 0 --no-cpu-baseline --no-exact-f32 > /dev/null 2>&1
+    rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/pmc_${cfg}_$grp -- python3 $R/bench.py --full --config $cfg --contigs $n --steps 1 --warmup 0 --no-cpu-baseline --no-exact-f32 > /dev/null 2>&1
   done
 done
 python3 - <<PY

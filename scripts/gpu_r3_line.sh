@@ -6,9 +6,9 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r3p
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default2 -- python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default2 -- python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cp $O/prof_default2/*/*kernel_stats.csv $O/default_kernel_stats.csv
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_small2 -- python3 $R/bench.py --config baseline500 > $O/bench_baseline500.json 2> $O/bench_baseline500.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_small2 -- python3 $R/bench.py --full --config baseline500 > $O/bench_baseline500.json 2> $O/bench_baseline500.err
 cp $O/prof_small2/*/*kernel_stats.csv $O/baseline500_kernel_stats.csv
 python3 -c "
 import json

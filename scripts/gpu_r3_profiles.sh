@@ -8,9 +8,9 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r3p
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cp $O/prof_default/*/*kernel_stats.csv $O/default_kernel_stats.csv
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_small -- python3 $R/bench.py --config baseline500 > $O/bench_baseline500.json 2> $O/bench_baseline500.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_small -- python3 $R/bench.py --full --config baseline500 > $O/bench_baseline500.json 2> $O/bench_baseline500.err
 cp $O/prof_small/*/*kernel_stats.csv $O/baseline500_kernel_stats.csv
 G_SQ="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA"
 for cfg in default baseline500; do
@@ -18,7 +18,7 @@ for cfg in default baseline500; do
   i=0
   for grp in "FETCH_SIZE" "WRITE_SIZE" "$G_SQ" "GRBM_GUI_ACTIVE"; do
     i=$((i+1))
-    timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/pmc_${cfg}_g$i -- python3 $R/bench.py --config $cfg --contigs $n --steps 1 --warmup 1 --no-cpu-baseline --no-exact-f32 --no-e2e > /dev/null 2> $O/pmc_${cfg}_g$i.err
+    timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/pmc_${cfg}_g$i -- python3 $R/bench.py --full --config $cfg --contigs $n --steps 1 --warmup 1 --no-cpu-baseline --no-exact-f32 --no-e2e > /dev/null 2> $O/pmc_${cfg}_g$i.err
   done
 done
 # the producer / consumer kernel (JG_OPT_CONV_PC = 1) through the same SQ / GRBM passes, an interleaved A/B against the
@@ -26,16 +26,16 @@ done
 i=4
 for grp in "$G_SQ" "GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/pmc_default_g$i -- python3 $R/bench.py --contigs 1500 --steps 1 --warmup 1 --no-cpu-baseline --no-exact-f32 --no-e2e --conv-pc 1 > /dev/null 2> $O/pmc_default_g$i.err
+  timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/pmc_default_g$i -- python3 $R/bench.py --full --contigs 1500 --steps 1 --warmup 1 --no-cpu-baseline --no-exact-f32 --no-e2e --conv-pc 1 > /dev/null 2> $O/pmc_default_g$i.err
 done
 ( cd $R
   for r in 1 2 3; do for pc in 0 1; do
-    timeout 300 python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-exact-f32 --no-e2e --conv-pc $pc > $O/ab_pc${pc}_$r.json 2>/dev/null
+    timeout 300 python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-exact-f32 --no-e2e --conv-pc $pc > $O/ab_pc${pc}_$r.json 2>/dev/null
     python3 -c "import json; d=json.load(open('$O/ab_pc${pc}_$r.json')); print('conv_pc=$pc round $r:', d['value'], 'Mbp/s  k5 frac', d['roofline']['frac'], ' avg launch ms', d['roofline']['avg_launch_ms'])"
   done; done > $O/pc_ab.txt
   cat $O/pc_ab.txt
   if [ -f jaeger_amd/libjaeger_hip_stamp.so ]; then
-    JAEGER_HIP_LIB=jaeger_amd/libjaeger_hip_stamp.so timeout 300 python3 bench.py --contigs 1500 --steps 1 --warmup 1 --no-cpu-baseline --no-exact-f32 --no-e2e --conv-pc 1 > /dev/null 2> $O/pc_stamp.err
+    JAEGER_HIP_LIB=jaeger_amd/libjaeger_hip_stamp.so timeout 300 python3 bench.py --full --contigs 1500 --steps 1 --warmup 1 --no-cpu-baseline --no-exact-f32 --no-e2e --conv-pc 1 > /dev/null 2> $O/pc_stamp.err
     grep PCSTAMP $O/pc_stamp.err | grep "rows=12288" | sort | uniq -c | sort -rn | head -0
     grep PCSTAMP $O/pc_stamp.err | grep "rows=12288" | tail -6 > $O/pc_stamps.txt; cat $O/pc_stamps.txt
   fi )

@@ -15,6 +15,6 @@ for i in 1 2 3; do
   for lib in $LIBS; do
     [ -f jaeger_amd/$lib ] || continue
     echo -n "$lib: "
-    JAEGER_HIP_LIB=$GRAFT_REPO_ROOT/jaeger_amd/$lib timeout 300 python bench.py --config baseline500 --no-cpu-baseline --no-exact-f32 --no-e2e 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline'].get('avg_launch_ms'))"
+    JAEGER_HIP_LIB=$PWD/jaeger_amd/$lib timeout 300 python bench.py --full --config baseline500 --no-cpu-baseline --no-exact-f32 --no-e2e 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline'].get('avg_launch_ms'))"
   done
 done | tee $O/ab.txt

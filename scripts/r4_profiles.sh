@@ -15,7 +15,7 @@ for cfg in default baseline500; do
   i=0
   for grp in "FETCH_SIZE" "WRITE_SIZE" "$G_SQ" "GRBM_GUI_ACTIVE"; do
     i=$((i+1))
-    timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/pmc_${cfg}_g$i -- python3 $R/bench.py --config $cfg --contigs $n --steps 1 --warmup 1 --no-cpu-baseline --no-exact-f32 --no-e2e > /dev/null 2> $O/pmc_${cfg}_g$i.err
+    timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/pmc_${cfg}_g$i -- python3 $R/bench.py --full --config $cfg --contigs $n --steps 1 --warmup 1 --no-cpu-baseline --no-exact-f32 --no-e2e > /dev/null 2> $O/pmc_${cfg}_g$i.err
   done
 done
 HASH=$(cd $R && python3 -c "import bench; print(bench.kernel_hash())")
@@ -78,9 +78,9 @@ json.dump(util, open(O + "/mfma_util.json", "w"), indent=1)
 print(json.dumps(util, indent=1)); print(json.dumps({k: v for k, v in traffic.items() if k[0] != "_"}, indent=1))
 PY
 cp $O/pmc_traffic.json $O/mfma_util.json $R/profiles/           # (this snapshot's copy: the lines below quote them)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python3 $R/bench.py > $O/r4_default_bench.json 2> $O/bench_default.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python3 $R/bench.py --full > $O/r4_default_bench.json 2> $O/bench_default.err
 cp $O/prof_default/*/*kernel_stats.csv $O/r4_default_bench_kernel_stats.csv
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_small -- python3 $R/bench.py --config baseline500 > $O/r4_baseline500_bench.json 2> $O/bench_baseline500.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_small -- python3 $R/bench.py --full --config baseline500 > $O/r4_baseline500_bench.json 2> $O/bench_baseline500.err
 cp $O/prof_small/*/*kernel_stats.csv $O/r4_baseline500_bench_kernel_stats.csv
 # kernel statistics of an end-to-end run (10 000-contig FASTA) of both families
 JAEGER_NO_CPROFILE=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_e2e_brain -- python3 $R/scripts/r4_e2e_prof.py brain 2 > $O/e2e_brain.log 2>&1

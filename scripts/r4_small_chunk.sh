@@ -4,7 +4,7 @@
 mkdir -p gpurun_out/r4chunk
 for rep in 1 2; do
   for c in 0 12288 24576 49152 65536; do
-    python bench.py --config baseline500 --chunk $c --steps 3 --warmup 1 --no-cpu-baseline --no-exact-f32 --no-e2e \
+    python bench.py --full --config baseline500 --chunk $c --steps 3 --warmup 1 --no-cpu-baseline --no-exact-f32 --no-e2e \
       2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('chunk $c', d['value'], d['ms_per_step'], d['roofline'].get('avg_launch_ms'))"
   done
 done | tee gpurun_out/r4chunk/run.log

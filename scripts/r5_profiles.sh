@@ -78,9 +78,9 @@ json.dump(util, open(O + "/mfma_util.json", "w"), indent=1)
 print(json.dumps(util, indent=1)); print(json.dumps({k: v for k, v in traffic.items() if k[0] != "_"}, indent=1))
 PY
 cp $O/pmc_traffic.json $O/mfma_util.json $R/profiles/           # (this snapshot's copy: the lines below quote them)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python3 $R/bench.py > $O/r5_default_bench.json 2> $O/bench_default.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python3 $R/bench.py --full > $O/r5_default_bench.json 2> $O/bench_default.err
 cp $O/prof_default/*/*kernel_stats.csv $O/r5_default_bench_kernel_stats.csv
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_small -- python3 $R/bench.py --config baseline500 --no-also > $O/r5_baseline500_bench.json 2> $O/bench_baseline500.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_small -- python3 $R/bench.py --full --config baseline500 --no-also > $O/r5_baseline500_bench.json 2> $O/bench_baseline500.err
 cp $O/prof_small/*/*kernel_stats.csv $O/r5_baseline500_bench_kernel_stats.csv
 # kernel statistics of an end-to-end run (10 000-contig FASTA) of both families
 JAEGER_NO_CPROFILE=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_e2e_brain -- python3 $R/scripts/r4_e2e_prof.py brain 2 > $O/e2e_brain.log 2>&1
@@ -94,12 +94,12 @@ for f in ('r5_default_bench.json','r5_baseline500_bench.json'):
     print(f, d['value'], r.get('frac'), (r.get('pmc_other_device') or {}).get('mfma_busy_frac'), (r.get('pmc_other_device') or {}).get('eff_clock_ghz'), r.get('traffic'), r.get('pmc_stale'), d.get('exact_f32_mbps'), e.get('mbps'), e.get('stages'))
 "
 grep '== ' $O/e2e_brain.log $O/e2e_b500.log
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_pyr -- python3 $R/bench.py --config pyramid --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --no-exact-f32 --no-also > $O/r5_pyramid_bench.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_pyr -- python3 $R/bench.py --full --config pyramid --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --no-exact-f32 --no-also > $O/r5_pyramid_bench.json 2>/dev/null
 cp $O/prof_pyr/*/*kernel_stats.csv $O/r5_pyramid_bench_kernel_stats.csv
 cd $R
-python3 bench.py > $O/r5_default_bench_plain.json 2> $O/plain_default.err
-python3 bench.py --config baseline500 --no-also > $O/r5_baseline500_bench_plain.json 2> $O/plain_b500.err
-python3 bench.py --config pyramid --no-also --no-e2e --no-cpu-baseline --steps 3 > $O/r5_pyramid_bench_plain.json 2> $O/plain_pyr.err
+python3 bench.py --full > $O/r5_default_bench_plain.json 2> $O/plain_default.err
+python3 bench.py --full --config baseline500 --no-also > $O/r5_baseline500_bench_plain.json 2> $O/plain_b500.err
+python3 bench.py --full --config pyramid --no-also --no-e2e --no-cpu-baseline --steps 3 > $O/r5_pyramid_bench_plain.json 2> $O/plain_pyr.err
 python3 -c "
 import json
 for f in ('r5_default_bench_plain.json','r5_baseline500_bench_plain.json','r5_pyramid_bench_plain.json','r5_pyramid_bench.json'):

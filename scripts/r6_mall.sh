@@ -17,7 +17,7 @@ for round in 1 2; do
   for c in $CHUNKS; do
     ( while true; do rocm-smi --showpower --showclocks --json 2>/dev/null | tr -d '\n'; echo; sleep 0.25; done ) > $O/power_c${c}_r$round.log &
     SM=$!
-    python3 $R/bench.py $COMMON --chunk $c > $O/plain_c${c}_r$round.json 2> $O/plain_c${c}_r$round.err
+    python3 $R/bench.py --full $COMMON --chunk $c > $O/plain_c${c}_r$round.json 2> $O/plain_c${c}_r$round.err
     kill $SM; wait $SM 2>/dev/null
   done
 done

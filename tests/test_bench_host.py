@@ -87,3 +87,29 @@ def test_pmc_fields_only_for_the_build_they_were_collected_on(tmp_path, monkeypa
     for args in (("default", "f32", 1500, 0, 2.8), ("default", "f16x3", 2000, 0, 2.8), ("default", "f16x3", 1500, 512, 2.8),
                  ("pyramid", "f16x3", 2000, 0, 1.0)):
         assert bench.pmc_fields(*args)["traffic"] is None
+
+
+def test_dump_outputs_writes_float32_and_samples_large_outputs(tmp_path):
+    """``--dump-outputs``: every array as ``<name>.npy`` in float32; above the byte cap, the same seeded rows of every
+    array (named by ``row_index.npy``), within the cap and identical from call to call."""
+    import numpy as np
+    rng = np.random.default_rng(7)
+    pred = rng.standard_normal((5000, 6)).astype(np.float32)
+    counts = rng.integers(0, 1500, (5000, 4)).astype(np.int32)
+    bench.dump_outputs(tmp_path / "small", {"prediction": pred, "counts": counts})
+    got = np.load(tmp_path / "small" / "prediction.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, pred)
+    got = np.load(tmp_path / "small" / "counts.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, counts.astype(np.float32))
+    assert not (tmp_path / "small" / "row_index.npy").exists()
+    cap = 40 * 1024
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, {"prediction": pred, "counts": counts}, max_bytes=cap)
+    idx = np.load(tmp_path / "a" / "row_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and 0 < idx.size < 5000
+    rows = idx.astype(np.int64)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "prediction.npy"), pred[rows])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "counts.npy"), counts[rows].astype(np.float32))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= cap + 3 * 128       # (+ the .npy headers)
+    for name in ("row_index", "prediction", "counts"):
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy"))

@@ -319,3 +319,31 @@ def test_bench_one_rank_over_rccl(tmp_path):
     a, b = np.load(tmp_path / "rccl.npy"), np.load(tmp_path / "plain.npy")
     assert a.shape == (400, 6) and np.abs(a).max() > 0
     np.testing.assert_array_equal(a, b)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_its_outputs(tmp_path):
+    """A plain ``bench.py`` run carries the headline only (no box, exact-f32, e2e, ``also`` or CPU baseline: ``--full``
+    adds them), times exactly ``--steps`` steps, and ``--dump-outputs`` writes the last step's arrays - the logits
+    ``--dump-gather`` sees, reliability and G/C/A/T counts - identically from run to run."""
+    base = [sys.executable, str(ROOT / "bench.py"), "--config", "frag1m", "--contigs", "400", "--steps", "3", "--warmup", "1"]
+    lines = []
+    for d in ("a", "b"):
+        res = subprocess.run(base + ["--dump-outputs", str(tmp_path / d), "--dump-gather", str(tmp_path / f"{d}.npy")],
+                             capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-4000:]
+        assert len(res.stdout.strip().splitlines()) == 1, res.stdout[-600:]
+        lines.append(json.loads(res.stdout.strip()))
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "Mbp/s" and line["higher_is_better"] is True and line["metric"].startswith("Mbp/s classified")
+    assert not {"box", "exact_f32_mbps", "e2e", "also"} & set(line) and line["cpu_baseline"] is None
+    pred = np.load(tmp_path / "a" / "prediction.npy")
+    assert pred.dtype == np.float32 and pred.shape == (400, 6) and np.abs(pred).max() > 0
+    np.testing.assert_array_equal(pred, np.load(tmp_path / "a.npy"))
+    counts = np.load(tmp_path / "a" / "counts.npy")
+    assert counts.shape == (400, 4) and (counts.sum(axis=1) == 1500).all()        # uniform ACGT, no N
+    assert np.load(tmp_path / "a" / "reliability.npy").shape[0] == 400
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    for name in names:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name))
