@@ -209,8 +209,26 @@ int jg_model_get_precision(const jg_model *m);
  * mode 1 (the others - 1x1 bypasses, widths or strides outside the kernel - run on the exact-f32 kernel with a layout
  * conversion either side: JG_MSTAT_LAYOUT_CONVERSIONS), JG_MSTAT_SMALL_FUSED = 1 when the whole conv stack runs as the
  * fused small-window kernel.  -1 for an unknown key. */
-enum { JG_MSTAT_CONVS = 0, JG_MSTAT_CONVS_F16X3 = 1, JG_MSTAT_LAYOUT_CONVERSIONS = 2, JG_MSTAT_SMALL_FUSED = 3 };
+enum { JG_MSTAT_CONVS = 0, JG_MSTAT_CONVS_F16X3 = 1, JG_MSTAT_LAYOUT_CONVERSIONS = 2, JG_MSTAT_SMALL_FUSED = 3,
+       JG_MSTAT_TAP_VARIANT = 4 };
 int64_t jg_model_get_stat(const jg_model *m, int key);
+/* ---- test readback: the tensor one op writes (tests/test_gpu_op_taps.py) ----
+ * jg_model_tap_shape: logical shape of what op `op` writes for id rows of l positions, PER WINDOW:
+ *   shape = (rows, frames, L_out, C) - rows = program rows per window (the strands of a two-strand model, else 1),
+ *   frames = frames per row; activations are f32, masks (JG_OP_MASK) u8 with C = 1.  From the program's shape walk.
+ * jg_model_set_tap: during the following jg_forward calls, after op `op` has been enqueued in each launch group the
+ *   library copies the tensor it wrote into host_dst (dst_bytes >= n_win x the shape's bytes), in logical layout at the
+ *   group's window offset: F16S tensors converted to f32 (hi + lo, exact), phase-split ones de-interleaved (they hold
+ *   the output times its mask).  op = -1 turns the tap off; one tap at a time; the forward of an untapped model is
+ *   unchanged.  JG_ERR_UNSUPPORTED (with the reason) for an op whose output is never stored: conv1 of a fused residual
+ *   block, a conv whose only reader is a fused max pool, the convs inside the fused small-window kernel or the table-net
+ *   kernel, pool / dense / vector ops; jg_predict_windows refuses to run while a tap is set.
+ * JG_MSTAT_TAP_VARIANT: JG_TAP_* bits of the tapped launches of the last jg_forward call (OR over its launch groups;
+ * still readable after the tap is turned off). */
+enum { JG_TAP_F16S = 1, JG_TAP_PHASE_SPLIT = 2, JG_TAP_WINDOW_PACKED = 4, JG_TAP_TABLE_LOOKUP = 8, JG_TAP_NARROW = 16,
+       JG_TAP_EXACT_F32 = 32, JG_TAP_FUSED_RESBLOCK = 64 };
+int jg_model_tap_shape(const jg_model *m, int op, int32_t l, int64_t shape[4]);
+int jg_model_set_tap(jg_model *m, int op, void *host_dst, int64_t dst_bytes);
 /* ... and conv by conv, as text (one line each: geometry -> kernel; for a conv on the exact-f32 kernel the rule that kept
  * it there), NUL-terminated, truncated to cap. */
 int jg_model_describe(const jg_model *m, char *buf, int64_t cap);

@@ -16,6 +16,7 @@ JG_MAX_BUFS = 6
 JG_MAX_VECS = 12
 JG_PTR_HOST, JG_PTR_DEVICE = 0, 1
 JG_BUF_NONE, JG_BUF_IDS = -1, -2
+JG_OK, JG_ERR_INVALID, JG_ERR_HIP, JG_ERR_UNSUPPORTED, JG_ERR_NOMEM, JG_ERR_IO = 0, -1, -2, -3, -4, -5   # jg_status
 JG_OPT_STREAM_BYTES = 1
 JG_OPT_CONV_PC = 2
 JG_OPT_TERMINI_EXACT = 3
@@ -28,6 +29,9 @@ JG_OPT_STREAM_PRIORITY = 9
 JG_COL_STRING, JG_COL_INT, JG_COL_FLOAT, JG_COL_BOOL, JG_COL_SPANS = 0, 1, 2, 3, 4     # jg_table_format column kinds
 JG_STAT_STREAM_GROUPS, JG_STAT_STREAM_BYTES, JG_STAT_PEAK_DEVICE_BASES, JG_STAT_DUST_MASKED, JG_STAT_WINDOWS_DONE = 1, 2, 3, 4, 5
 JG_MSTAT_CONVS, JG_MSTAT_CONVS_F16X3, JG_MSTAT_LAYOUT_CONVERSIONS, JG_MSTAT_SMALL_FUSED = 0, 1, 2, 3
+JG_MSTAT_TAP_VARIANT = 4
+# JG_MSTAT_TAP_VARIANT bits: the kernel variant the tapped op ran on (jg_model_set_tap)
+TAP_F16S, TAP_PHASE_SPLIT, TAP_WINDOW_PACKED, TAP_TABLE_LOOKUP, TAP_NARROW, TAP_EXACT_F32, TAP_FUSED_RESBLOCK = 1, 2, 4, 8, 16, 32, 64
 
 # jg_op_kind
 OP_CONV, OP_MASK, OP_POOL, OP_DENSE, OP_ELTWISE, OP_NMD_FINAL, OP_OODSIG, OP_MAXPOOL1D, OP_FRAMESUM, OP_STRANDS, OP_EMBED, OP_VECMAX = range(1, 13)
@@ -92,6 +96,8 @@ SYMBOLS = {
     "jg_model_get_precision": (C.c_int, [_vp]),
     "jg_model_get_stat": (C.c_int64, [_vp, C.c_int]),
     "jg_model_describe": (C.c_int, [_vp, C.c_char_p, C.c_int64]),
+    "jg_model_tap_shape": (C.c_int, [_vp, C.c_int, C.c_int32, _i64p]),
+    "jg_model_set_tap": (C.c_int, [_vp, C.c_int, _vp, C.c_int64]),
     "jg_encode": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_int, C.c_int64, C.c_int32, _vp,
                             C.c_int32, C.c_int32, _vp, _vp, C.c_int, _vp]),
     "jg_forward": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int,

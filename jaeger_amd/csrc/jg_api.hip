@@ -447,7 +447,7 @@ static bool tab_usable(const jg_model *m, int l) {
 
 static int plan_shapes(jg_model *m, int l, int64_t act_elems[JG_MAX_BUFS],
                        int64_t msk_elems[JG_MAX_BUFS], int64_t nmd_elems[JG_MAX_BUFS],
-                       int vec_w[JG_MAX_VECS], double *flops) {
+                       int vec_w[JG_MAX_VECS], double *flops, int tap_op = -1, int64_t *tap_shape = nullptr) {
   Shape sh[JG_MAX_BUFS];
   int mlen[JG_MAX_BUFS] = {};   // positions per window of each mask slot
   for (int i = 0; i < JG_MAX_BUFS; ++i) act_elems[i] = msk_elems[i] = nmd_elems[i] = 0;
@@ -545,6 +545,14 @@ static int plan_shapes(jg_model *m, int l, int64_t act_elems[JG_MAX_BUFS],
         break;
       default:
         break;
+    }
+    if ((int)i == tap_op && tap_shape != nullptr) {      // jg_model_tap_shape: the tensor this op wrote, per window
+      tap_shape[0] = m->strands;
+      if (op.kind == JG_OP_MASK) {
+        tap_shape[1] = m->id_frames; tap_shape[2] = mlen[op.out_mask] / m->id_frames; tap_shape[3] = 1;
+      } else if (op.out_buf >= 0) {
+        tap_shape[1] = sh[op.out_buf].frames; tap_shape[2] = sh[op.out_buf].L; tap_shape[3] = sh[op.out_buf].C;
+      }
     }
   }
   for (int i = 0; i < JG_MAX_VECS; ++i) vec_w[i] = (vec_w[i] + 3) & ~3;  // float4-aligned rows
@@ -1546,6 +1554,7 @@ extern "C" int64_t jg_model_get_stat(const jg_model *m, int key) {
     case JG_MSTAT_CONVS_F16X3: return n_f16;
     case JG_MSTAT_LAYOUT_CONVERSIONS: return m->f16_eligible ? n_cvt : 0;
     case JG_MSTAT_SMALL_FUSED: return m->small != nullptr ? 1 : 0;
+    case JG_MSTAT_TAP_VARIANT: return m->tap_variant;
     default: return -1;
   }
 }
@@ -1617,6 +1626,9 @@ static void free_workspace(jg_model *m) {
   if (m->cvt_scratch) (void)hipFree(m->cvt_scratch);
   m->cvt_scratch = nullptr;
   m->cvt_cap = 0;
+  if (m->tap_buf) (void)hipFree(m->tap_buf);
+  m->tap_buf = nullptr;
+  m->tap_cap = 0;
 }
 
 extern "C" int jg_model_destroy(jg_model *m) {
@@ -1737,6 +1749,126 @@ static int grow(T **p, int64_t *cap, int64_t need_bytes) {
 
 // Run the op program over `nw` windows whose ids (nw, 6, l) are on the device (a two-strand model: nw = strand rows,
 // ids (nw, 1, l)).
+// ---------------------------------------------------------------------------
+// test readback (jg_model_set_tap)
+// ---------------------------------------------------------------------------
+// why op i's output is never stored under the model's current placement, or nullptr
+static const char *tap_refusal(const jg_model *m, size_t i, char *why, size_t cap) {
+  const jg_op &op = m->ops[i];
+  if (op.kind != JG_OP_CONV && op.kind != JG_OP_MASK && op.kind != JG_OP_ELTWISE && op.kind != JG_OP_EMBED &&
+      op.kind != JG_OP_MAXPOOL1D && op.kind != JG_OP_FRAMESUM) {
+    snprintf(why, cap, "op %zu (kind %d) writes a vector or nothing - pool, dense and vector results are outputs already", i, op.kind);
+    return why;
+  }
+  if (op.kind != JG_OP_CONV || m->precision != 1 || !m->f16_eligible || !m->hprep[i].f16_ok) return nullptr;
+  const ConvHPrep &hp = m->hprep[i];
+  if (hp.rb_second >= 0 && m->e->fuse_resblock != 0) {
+    snprintf(why, cap, "op %zu is conv1 of a fused residual block: op %d computes it in LDS and stores only the block's "
+             "output (engine option JG_OPT_FUSE_RESBLOCK 0 exposes it)", i, hp.rb_second);
+    return why;
+  }
+  if (hp.pool_op >= 0) {
+    snprintf(why, cap, "op %zu is store-free: its only reader, the masked max pool op %d, is fused into its epilogue", i, hp.pool_op);
+    return why;
+  }
+  return nullptr;
+}
+
+static int tap_copy(jg_model *m, size_t i, const Shape *sh, const int *mlen, int nw, hipStream_t s) {
+  const jg_op &op = m->ops[i];
+  char why[256];
+  if (tap_refusal(m, i, why, sizeof(why)) != nullptr) {
+    jg_set_error("tap: %s", why);
+    return JG_ERR_UNSUPPORTED;
+  }
+  uint8_t *dst = static_cast<uint8_t *>(m->tap_dst);
+  if (op.kind == JG_OP_MASK) {
+    const int64_t per_row = mlen[op.out_mask];                       // frames x L_out bytes per program row
+    JG_REQUIRE((m->tap_row0 + nw) * per_row <= m->tap_bytes, JG_ERR_INVALID, "tap: destination of %lld bytes too small",
+               (long long)m->tap_bytes);
+    JG_HIP(hipMemcpyAsync(dst + m->tap_row0 * per_row, m->msk[op.out_mask], (size_t)(nw * per_row), hipMemcpyDeviceToHost, s));
+    JG_HIP(hipStreamSynchronize(s));
+    return JG_OK;
+  }
+  const Shape t = sh[op.out_buf];
+  const int64_t per_row = (int64_t)t.frames * t.L * t.C * (int64_t)sizeof(float);
+  const int64_t rows = (int64_t)nw * t.frames;
+  JG_REQUIRE((m->tap_row0 + nw) * per_row <= m->tap_bytes, JG_ERR_INVALID, "tap: destination of %lld bytes too small",
+             (long long)m->tap_bytes);
+  // the slot's layout, from the format plan
+  const ConvHPrep &hp = m->hprep[i];
+  const bool f16_conv = op.kind == JG_OP_CONV && m->precision == 1 && m->f16_eligible && hp.f16_ok;
+  const bool rb = f16_conv && hp.rb_first >= 0 && m->e->fuse_resblock != 0;
+  const bool psplit = f16_conv && hp.ps_store;
+  const bool f16s = psplit || rb || (f16_conv && hp.out_f16s) || (op.kind == JG_OP_MAXPOOL1D && m->precision == 1 && hp.pool_f16s);
+  int64_t v = 0;
+  if (f16s) v |= JG_TAP_F16S;
+  if (psplit) v |= JG_TAP_PHASE_SPLIT;
+  if (rb) v |= JG_TAP_FUSED_RESBLOCK;
+  if (op.kind == JG_OP_CONV) {
+    if (!f16_conv) v |= JG_TAP_EXACT_F32;
+    if (f16_conv && !rb && m->tap_flat) v |= JG_TAP_WINDOW_PACKED;
+    if (f16_conv && hp.d_lut != nullptr) v |= JG_TAP_TABLE_LOOKUP;
+    if (f16_conv && hp.cw != 128) v |= JG_TAP_NARROW;
+  }
+  m->tap_variant |= v;
+  float *out = reinterpret_cast<float *>(dst + m->tap_row0 * per_row);
+  if (!f16s) {
+    JG_HIP(hipMemcpyAsync(out, m->act[op.out_buf], (size_t)(nw * per_row), hipMemcpyDeviceToHost, s));
+    JG_HIP(hipStreamSynchronize(s));
+    return JG_OK;
+  }
+  // F16S [rows][C/16][hi|lo][2][L] -> f32 (rows, L, C); a phase-split tensor is an F16S tensor of (L + 1) / 2 positions
+  // and 2C channels (position p of channel c at position p / 2, channel (p & 1) C + c)
+  const int L2 = psplit ? (t.L + 1) / 2 : t.L, C2 = psplit ? 2 * t.C : t.C;
+  const int64_t need = rows * L2 * (int64_t)C2 * (int64_t)sizeof(float);
+  int rc = grow(&m->tap_buf, &m->tap_cap, need);
+  if (rc != JG_OK) return rc;
+  if ((rc = jg_launch_f16s_to_f32(reinterpret_cast<const uint4 *>(m->act[op.out_buf]), rows, L2, C2, m->tap_buf, s)) != JG_OK)
+    return rc;
+  if (!psplit) {
+    JG_HIP(hipMemcpyAsync(out, m->tap_buf, (size_t)need, hipMemcpyDeviceToHost, s));
+    JG_HIP(hipStreamSynchronize(s));
+    return JG_OK;
+  }
+  std::vector<float> tmp((size_t)(need / sizeof(float)));
+  JG_HIP(hipMemcpyAsync(tmp.data(), m->tap_buf, (size_t)need, hipMemcpyDeviceToHost, s));
+  JG_HIP(hipStreamSynchronize(s));
+  for (int64_t r = 0; r < rows; ++r)
+    for (int p = 0; p < t.L; ++p)
+      memcpy(out + (r * t.L + p) * t.C, tmp.data() + (r * L2 + p / 2) * C2 + (p & 1) * t.C, (size_t)t.C * sizeof(float));
+  return JG_OK;
+}
+
+extern "C" int jg_model_tap_shape(const jg_model *m, int op, int32_t l, int64_t shape[4]) {
+  JG_REQUIRE(m != nullptr && shape != nullptr && l > 0 && op >= 0 && op < (int)m->ops.size(), JG_ERR_INVALID,
+             "jg_model_tap_shape: bad arguments");
+  int64_t a[JG_MAX_BUFS], b[JG_MAX_BUFS], c[JG_MAX_BUFS];
+  int vw[JG_MAX_VECS];
+  for (int q = 0; q < 4; ++q) shape[q] = 0;
+  int rc = plan_shapes(const_cast<jg_model *>(m), l, a, b, c, vw, nullptr, op, shape);
+  if (rc != JG_OK) return rc;
+  JG_REQUIRE(shape[1] > 0, JG_ERR_UNSUPPORTED, "jg_model_tap_shape: op %d (kind %d) writes no tensor", op, m->ops[(size_t)op].kind);
+  return JG_OK;
+}
+
+extern "C" int jg_model_set_tap(jg_model *m, int op, void *host_dst, int64_t dst_bytes) {
+  JG_REQUIRE(m != nullptr && op >= -1 && op < (int)m->ops.size(), JG_ERR_INVALID, "jg_model_set_tap: bad arguments");
+  if (op >= 0) {
+    JG_REQUIRE(host_dst != nullptr && dst_bytes > 0, JG_ERR_INVALID, "jg_model_set_tap: no destination");
+    char why[256];
+    if (tap_refusal(m, (size_t)op, why, sizeof(why)) != nullptr) {
+      jg_set_error("jg_model_set_tap: %s", why);
+      return JG_ERR_UNSUPPORTED;
+    }
+  }
+  m->tap_op = op;
+  m->tap_dst = op >= 0 ? host_dst : nullptr;
+  m->tap_bytes = op >= 0 ? dst_bytes : 0;
+  if (op >= 0) m->tap_variant = 0;                    // (turning the tap off keeps the last forward's bits readable)
+  return JG_OK;
+}
+
 static int run_chunk(jg_model *m, const uint8_t *d_ids, int nw, int l, hipStream_t s) {
   jg_engine *e = m->e;
   Shape sh[JG_MAX_BUFS];
@@ -1785,6 +1917,8 @@ static int run_chunk(jg_model *m, const uint8_t *d_ids, int nw, int l, hipStream
     const jg_op &op = m->ops[i];
     int rc = JG_OK;
     if (small && (int)i < m->small->pool_op) {
+      JG_REQUIRE((int)i != m->tap_op, JG_ERR_UNSUPPORTED,
+                 "tap: op %zu runs inside the fused small-window kernel at rows of %d positions (no tensor is stored)", i, l);
       if (op.kind == JG_OP_NMD_FINAL) {             // finish the tap the fused kernel accumulated for this slot
         const JgSmallNet *sn = m->small;
         int tap = 0;
@@ -1813,6 +1947,8 @@ static int run_chunk(jg_model *m, const uint8_t *d_ids, int nw, int l, hipStream
     }
     if (tab && (int)i == m->tab_pool) continue;
     if (tab && (int)i == m->tab_conv) {
+      JG_REQUIRE((int)i != m->tap_op, JG_ERR_UNSUPPORTED,
+                 "tap: op %zu runs inside the table-net strand kernel (conv + pool in one launch, no tensor is stored)", i);
       const jg_op &po = m->ops[(size_t)m->tab_pool];
       int lo, pl;
       conv_geometry(l, op.k, 1, op.dilation, op.padding, &lo, &pl);
@@ -1874,6 +2010,7 @@ static int run_chunk(jg_model *m, const uint8_t *d_ids, int nw, int l, hipStream
           JG_HIP(hipEventRecord(pe.a, s));
         }
         const bool rb_on = prec == 1 && e->fuse_resblock != 0;
+        m->tap_flat = 0;
         if (rb_on && m->hprep[i].f16_ok && m->hprep[i].rb_second >= 0) {
           // first conv of a fused residual block: computed by the second conv's launch (jg_resblock.hip)
           sh[op.out_buf] = Shape{in.frames, lo, op.cout};
@@ -1986,6 +2123,7 @@ static int run_chunk(jg_model *m, const uint8_t *d_ids, int nw, int l, hipStream
               a.flat_inv_p = 1.0f / (float)fp;
               a.flat_inv_wp = 1.0f / (float)wp;
               strips_per_win = wp / (256 / strips);
+              m->tap_flat = 1;
             }
           }
           if (hp.nmd_slot >= 0) m->part_rows[hp.nmd_slot] = strips_per_win;
@@ -2153,6 +2291,7 @@ static int run_chunk(jg_model *m, const uint8_t *d_ids, int nw, int l, hipStream
         return JG_ERR_UNSUPPORTED;
     }
     if (rc != JG_OK) return rc;
+    if ((int)i == m->tap_op && (rc = tap_copy(m, i, sh, mlen, nw, s)) != JG_OK) return rc;
   }
   return JG_OK;
 }
@@ -2238,6 +2377,7 @@ static int forward_chunks(jg_model *m, const uint8_t *d_ids, int64_t n_win, int 
   const int w_emb = jg_model_vec_width(m, 2), w_nmd = jg_model_vec_width(m, 3);
   for (int64_t w0 = 0; w0 < n_win; w0 += chunk) {
     const int nw = (int)std::min<int64_t>(chunk, n_win - w0);
+    m->tap_row0 = w0 * m->strands;
     int rc = run_chunk(m, d_ids + w0 * m->strands * m->id_frames * (int64_t)l * m->id_bytes, nw * m->strands, l, s);
     if (rc != JG_OK) return rc;
     if ((rc = copy_out(m, 2, w_pred, prediction, w0, nw, out_loc, s)) != JG_OK) return rc;
@@ -2281,6 +2421,7 @@ extern "C" int jg_forward(jg_model *m, const uint8_t *ids, int ids_loc, int64_t 
   jg_engine *e = m->e;
   JG_HIP(hipSetDevice(e->dev));
   hipStream_t s = pick_stream(e, stream);
+  m->tap_variant = 0;
   const uint8_t *d_ids = ids;
   if (ids_loc == JG_PTR_HOST) {
     const int64_t bytes = n_win * m->strands * m->id_frames * (int64_t)l * m->id_bytes;
@@ -2702,6 +2843,8 @@ extern "C" int jg_predict_windows(jg_model *m, const uint8_t *bases, int64_t n_b
   JG_REQUIRE(m != nullptr && bases != nullptr && win_start != nullptr && win_len != nullptr &&
                  lut65 != nullptr && n_win >= 0,
              JG_ERR_INVALID, "jg_predict_windows: bad arguments");
+  JG_REQUIRE(m->tap_op < 0, JG_ERR_UNSUPPORTED, "jg_predict_windows: a tap is set (op %d): taps are read through jg_forward only",
+             m->tap_op);
   jg_engine *e = m->e;
   e->windows_done.store(0, std::memory_order_release);       // (also for an empty call: a poller must not see the previous call's mark)
   if (n_win == 0) return JG_OK;

@@ -316,6 +316,15 @@ struct jg_model {
   int tab_act = 0, tab_cq = 0, tab_vocab = 0, tab_zero = 0;   // table rows incl. an appended zero row when row 0 is not one
   int part_rows[JG_MAX_BUFS] = {};  // split-f16 path: partial rows per window the last conv wrote to each NMD slot
   int pool_rows = 0;                // same for the fused max pool
+  // test readback (jg_model_set_tap): the tensor op tap_op writes, copied in logical layout into tap_dst after the op
+  int tap_op = -1;
+  void *tap_dst = nullptr;
+  int64_t tap_bytes = 0;
+  int64_t tap_row0 = 0;             // first program row of the running chunk
+  int64_t tap_variant = 0;          // JG_TAP_* bits of the tapped launches of the last jg_forward call
+  int tap_flat = 0;                 // window-packed tiling of the conv launch run_chunk enqueued last
+  float *tap_buf = nullptr;         // F16S -> f32 conversion target of the tap (never the live cvt_scratch)
+  int64_t tap_cap = 0;              // bytes
 };
 
 // cores this process may use: affinity mask, cgroup CPU quota, divided by LOCAL_WORLD_SIZE (jg_dust.hip)

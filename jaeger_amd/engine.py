@@ -308,6 +308,27 @@ class HipModel:
                                     L.JG_PTR_HOST, int(chunk), None), "jg_forward")
         return {k: v for k, v in o.items() if v is not None}
 
+    def tap(self, op: int, ids: np.ndarray, chunk: int = 0) -> np.ndarray:
+        """Forward ``ids`` and return the tensor op ``op`` wrote (``jg_model_set_tap``): f32 (W x rows, frames, L_out, C) for an
+        activation, u8 (W x rows, frames, L_out) for a mask op.  The tap is off again when this returns."""
+        ids = np.ascontiguousarray(ids, np.uint16 if self.wide_ids else np.uint8)
+        shape = (C.c_int64 * 4)()
+        L.check(self.lib.jg_model_tap_shape(self.handle, int(op), ids.shape[2], shape), "jg_model_tap_shape")
+        rows, frames, l_out, c = (int(v) for v in shape)
+        is_mask = self.program.ops[op].kind == L.OP_MASK
+        out = np.zeros((ids.shape[0] * rows, frames, l_out) if is_mask else (ids.shape[0] * rows, frames, l_out, c),
+                       np.uint8 if is_mask else np.float32)
+        L.check(self.lib.jg_model_set_tap(self.handle, int(op), _ptr(out), out.nbytes), "jg_model_set_tap")
+        try:
+            self.forward(ids, chunk=chunk, want=())
+        finally:
+            self.lib.jg_model_set_tap(self.handle, -1, None, 0)
+        return out
+
+    def tap_variant(self) -> int:
+        """``JG_TAP_*`` bits of the kernel variant the last tapped forward ran the op on."""
+        return int(self.lib.jg_model_get_stat(self.handle, L.JG_MSTAT_TAP_VARIANT))
+
     def predict_windows(self, bases, n_bases: int, win_start, win_len, n_win: int, fsize: int, lut,
                         flags: int = 0, l_pad: int | None = None, chunk: int = 0, device_inputs=False,
                         want=("prediction", "reliability", "embedding", "nmd"), counts=True, out: dict | None = None):
