@@ -271,11 +271,17 @@ void conv_f16x3_kernel(ConvHArgs a) {
   };
   // after a slice's DMA has landed: overwrite padding / masked-out pieces with zeros (by the
   // lanes that fetched them); the step barrier then publishes the slice
+  // (which iterations hold a piece of this lane at all, as bits of one register: as five per-lane conditions they are
+  // five loop-invariant lane masks in scalar register pairs, alive - or spilled - through the whole kernel)
+  unsigned a_has = 0;
+#pragma unroll
+  for (int it = 0; it < A_ITERS; ++it) a_has |= ((a_pk[it] >> 20) < NT ? 1u : 0u) << it;
   auto zero_fill = [&](int buf) {
     uint4 *A = Abuf + buf * a_items;
+    const unsigned zf = a_has & ~x_ok;
 #pragma unroll
     for (int it = 0; it < A_ITERS; ++it)
-      if ((a_pk[it] >> 20) < NT && !((x_ok >> it) & 1u)) A[tid + it * HT] = make_uint4(0u, 0u, 0u, 0u);
+      if ((zf >> it) & 1u) A[tid + it * HT] = make_uint4(0u, 0u, 0u, 0u);
   };
 
   f32x16 acc[TM][TN];       // [tm: position block][tn: channel block]
@@ -963,20 +969,98 @@ void conv_f16x3_kernel(ConvHArgs a) {
         }
         return live;
       };
+      // The 128-channel instantiations (no run-time geometry) resolve a lane's output position ONCE per tile and
+      // position block - om[tm]: its mask byte, ob[tm]: its first output / shortcut item, olive: "position exists" - and
+      // every access of the epilogue is (wave-uniform base + wave-uniform item offset) + this 32-bit lane offset: the
+      // uniform part is scalar arithmetic, the access takes the lane offset as it is.  Row-tiled launches keep the row in
+      // the uniform base (the lane offset is a byte offset inside one row); window-packed ones, whose tiles span rows, carry
+      // it in the lane offset (items).  Before, prefetch / epi_block / store_block each resolved the position again and
+      // built 64-bit item addresses per access, out of scalars that had been spilled to register lanes by then.
+      constexpr bool OPOS = !GEN;
+      unsigned ob[TM], om[TM], olive = 0;
+      size_t o_row = 0, o_mrow = 0;          // row-tiled: offset of the tile's row in y / addh (bytes), in mask_out
+      unsigned o_step = 0;                   // items (window-packed) / bytes between a lane's consecutive items: 2 L_out
+      // ... and read the arguments the addressing needs from the kernarg segment here, per tile (scalar loads), instead
+      // of keeping them alive - that is: spilled - across the main loop
+      const void *e_y = a.y, *e_addh = a.addh;
+      const uint8_t *e_mask = a.mask_out;
+      int e_dbg = a.dbg, e_f16s = a.out_f16s;
+      float *e_pool = a.pool_out, *e_nmd = a.nmd_out;
+      int *e_overflow = a.overflow;
+      if constexpr (OPOS) {
+        typedef const __attribute__((address_space(4))) ConvHArgs *KArgs;      // the only explicit argument: offset 0
+        KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        e_addh = ka->addh;
+        e_mask = ka->mask_out;
+        e_dbg = ka->dbg;
+        e_f16s = ka->out_f16s;
+        e_nmd = ka->nmd_out;
+        const unsigned Lo = (unsigned)ka->L_out, CC4 = (unsigned)(ka->cout_pad >> 4) * 4u;
+        o_step = FLAT ? 2u * Lo : 32u * Lo;
+        // (opaque on purpose: as a loop invariant the compiler multiplies it out into one 64-bit offset per item of the
+        // wave, hoists those out of the tile loop and spills them - sixteen lane-read pairs per tile to save sixteen
+        // scalar multiplications)
+        asm volatile("" : "+s"(o_step));
+        if constexpr (!FLAT) {
+          o_row = (size_t)cur[0].rowblk * CC4 * Lo * 16u + (size_t)(wn * 8) * o_step;
+          o_mrow = (size_t)cur[0].rowblk * Lo;
+        }
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm) {
+          int row, p;          // (out_pos() without run-time geometry, on the length read above)
+          const bool live = resolve(cur[0], (wm * TM + tm) * 32 + i, (int)Lo, row, p);
+          const int mc = live ? p : 0;
+          if constexpr (FLAT) {
+            if (!live) row = min(max(row, 0), a.rows - 1);
+          }
+          if (live) olive |= 1u << tm;
+          if constexpr (FLAT) {
+            om[tm] = (unsigned)row * Lo + (unsigned)mc;
+            ob[tm] = ((unsigned)row * CC4 + (unsigned)h) * Lo + (unsigned)mc;
+          } else {
+            om[tm] = (unsigned)mc;
+            ob[tm] = ((unsigned)h * Lo + (unsigned)mc) * 16u;
+          }
+        }
+      }
+      // address of item (channel chunk 2 * (wn * 2 + tn) + j, plane, lane half h) of position block tm in y / addh
+      auto o_item = [&](const void *base, int tm, int tn, int j, int plane) -> const char * {
+        if constexpr (FLAT) {
+          return reinterpret_cast<const char *>(base) + ((size_t)(ob[tm] + (unsigned)(((wn * 2 + tn) * 2 + j) * 2 + plane) * o_step) << 4);
+        } else {
+          return reinterpret_cast<const char *>(base) + (o_row + (size_t)((unsigned)((tn * 2 + j) * 2 + plane) * o_step)) + ob[tm];
+        }
+      };
+      auto o_maskbyte = [&](int tm) -> unsigned char {
+        return e_mask != nullptr ? (e_mask + o_mrow)[om[tm]] : (unsigned char)1;
+      };
       auto prefetch = [&](Pre &p, const Tile &tile, int tm, int tn) {
         const int nb = (wn * 2 + tn) * 32;
-        int orow, mc;
-        out_pos(tile, tm, orow, mc);
-        p.mkb = a.mask_out != nullptr ? a.mask_out[(size_t)orow * a.L_out + mc] : (unsigned char)1;
-        if (a.addh != nullptr && !(a.dbg & 128)) {
+        int orow = 0, mc = 0;
+        if constexpr (OPOS) {
+          p.mkb = o_maskbyte(tm);
+        } else {
+          out_pos(tile, tm, orow, mc);
+          p.mkb = a.mask_out != nullptr ? a.mask_out[(size_t)orow * a.L_out + mc] : (unsigned char)1;
+        }
+        if (e_addh != nullptr && !(e_dbg & 128)) {
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
-            // (a 16-channel chunk past the tensor's width - zero-padded weights - reads the last real chunk: unused)
-            const unsigned it4 = item4(orow, mc, (!GEN || nb + ch0 + 16 * j < a.cout) ? nb : 0, j);
-            // (read once, like the activation slices: non-temporal)
             typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-            const u32x4 nh = ld_stream(reinterpret_cast<const u32x4 *>(a.addh + it4));   // whole item of group 2j+h
-            const u32x4 nl = ld_stream(reinterpret_cast<const u32x4 *>(a.addh + it4 + 2u * (unsigned)a.L_out));
+            const u32x4 *src_h, *src_l;
+            if constexpr (OPOS) {
+              src_h = reinterpret_cast<const u32x4 *>(o_item(e_addh, tm, tn, j, 0));
+              src_l = reinterpret_cast<const u32x4 *>(o_item(e_addh, tm, tn, j, 1));
+            } else {
+              // (a 16-channel chunk past the tensor's width - zero-padded weights - reads the last real chunk: unused)
+              const unsigned it4 = item4(orow, mc, (!GEN || nb + ch0 + 16 * j < a.cout) ? nb : 0, j);
+              src_h = reinterpret_cast<const u32x4 *>(a.addh + it4);
+              src_l = reinterpret_cast<const u32x4 *>(a.addh + it4 + 2u * (unsigned)a.L_out);
+            }
+            // (read once, like the activation slices: non-temporal)
+            const u32x4 nh = ld_stream(src_h);   // whole item of group 2j+h
+            const u32x4 nl = ld_stream(src_l);
             uint4 vh = make_uint4(nh[0], nh[1], nh[2], nh[3]);
             uint4 vl = make_uint4(nl[0], nl[1], nl[2], nl[3]);
             // give each lane back its own 4 channels of groups 2j and 2j+1
@@ -997,8 +1081,13 @@ void conv_f16x3_kernel(ConvHArgs a) {
         Pre p;
         prefetch(p, tile, tm, tn);
         const int nb = (wn * 2 + tn) * 32;
-        int orow_, mc_;
-        const bool live = out_pos(tile, tm, orow_, mc_);
+        bool live;
+        if constexpr (OPOS) {
+          live = ((olive >> tm) & 1u) != 0u;
+        } else {
+          int orow_, mc_;
+          live = out_pos(tile, tm, orow_, mc_);
+        }
         const float mk = p.mkb != 0 ? 1.f : 0.f;
         // ---- stage primitives on this lane's 16 channels of one position -----------------
         auto st_affine = [&](int row) {
@@ -1069,7 +1158,7 @@ void conv_f16x3_kernel(ConvHArgs a) {
         if constexpr (EP == JG_EP_GENERIC) {
           // any stage list: interpreted at run time (slow path: the accumulators bounce through
           // the interpreter's switch); the model families in-tree all hit a compiled pattern
-          for (int q = 0; q < ((a.dbg & 32) ? 0 : a.n_hst); ++q) {
+          for (int q = 0; q < ((e_dbg & 32) ? 0 : a.n_hst); ++q) {
             const HStageArg st = a.hst[q];
             switch (st.kind) {
               case JG_HST_AFFINE: st_affine(st.pad_); break;
@@ -1103,7 +1192,7 @@ void conv_f16x3_kernel(ConvHArgs a) {
           if (n2 == 1) st_affine(n1 ? 2 : 1);
           else if (n2 == 2) st_dyt(n1 ? 2 : 1, a.alpha2, a.dytmask2);
           if (e_ & JG_EP_ACT2) st_gelu();
-        } else if (!(a.dbg & 32)) {
+        } else if (!(e_dbg & 32)) {
           // compiled pattern: affine [nmd] [norm1] [add] [gelu] [nmd] [norm2] [gelu], straight line
           constexpr int N1 = (EP >> 1) & 3, N2 = (EP >> 6) & 3;
           st_affine(0);
@@ -1126,7 +1215,7 @@ void conv_f16x3_kernel(ConvHArgs a) {
         // results stay in the block's registers (F16S: re-split, lane-pair swapped and bit-cast,
         // dword 4j..4j+3 = hi item, 8+4j.. = lo item of group 2j+h); stored by store_block() once
         // every block's loads are done - no load ever queues behind a store
-        if (a.out_f16s) {
+        if (e_f16s) {
           uint2 ph[4], pl[4];
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
@@ -1159,12 +1248,39 @@ void conv_f16x3_kernel(ConvHArgs a) {
           }
         }
       };
-      auto store_block = [&](const f32x16 &x, const Tile &tile, int tm, int tn) {
+      char *f32_base = nullptr;              // f32 output: the wave's first channel in the tile's row (row-tiled) / in y
+      auto store_block = [&](const f32x16 &x, const Tile &tile, int tm, int tn, bool f16s) {
         const int nb = (wn * 2 + tn) * 32;
+        if constexpr (OPOS) {        // (the caller has tested the output kind and the ablation switch once per tile, olive
+                                     // once per position block)
+          typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+          if (f16s) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              const u32x4 vhi = {__float_as_uint(x[4 * j]), __float_as_uint(x[4 * j + 1]),
+                                 __float_as_uint(x[4 * j + 2]), __float_as_uint(x[4 * j + 3])};
+              const u32x4 vlo = {__float_as_uint(x[8 + 4 * j]), __float_as_uint(x[8 + 4 * j + 1]),
+                                 __float_as_uint(x[8 + 4 * j + 2]), __float_as_uint(x[8 + 4 * j + 3])};
+              // (streamed: see the run-time-geometry form below)
+              st_stream(vhi, reinterpret_cast<u32x4 *>(const_cast<char *>(o_item(e_y, tm, tn, j, 0))));
+              st_stream(vlo, reinterpret_cast<u32x4 *>(const_cast<char *>(o_item(e_y, tm, tn, j, 1))));
+            }
+          } else {
+            // f32 (rows, L_out, 128 channels - these instantiations are only launched at that width): om[tm] is the
+            // position, inside the tile's row when row-tiled
+            char *yf = f32_base + tn * (32 * 4);
+            if constexpr (FLAT) yf += ((size_t)om[tm] * (HN * 4) + 16 * h);
+            else yf += om[tm] * (unsigned)(HN * 4) + 16u * (unsigned)h;
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+              *reinterpret_cast<float4 *>(yf + 32 * g) = make_float4(x[4 * g], x[4 * g + 1], x[4 * g + 2], x[4 * g + 3]);
+          }
+          return;
+        }
         int orow, mc;
         const bool live = out_pos(tile, tm, orow, mc);
-        if (live && !(a.dbg & 64)) {
-          if (a.out_f16s) {
+        if (live && !(e_dbg & 64)) {
+          if (e_f16s) {
             uint4 *yh = reinterpret_cast<uint4 *>(a.y);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -1234,9 +1350,9 @@ void conv_f16x3_kernel(ConvHArgs a) {
         const float v = lane_reduce(nmd_acc, [](float x, float y) { return x + y; });
         int ch;
         const size_t slot = reduced_slot(tile, tn, ch);
-        if (i < 16 && tile.valid && ch < a.cout) a.nmd_out[slot] = v;
+        if (i < 16 && tile.valid && ch < a.cout) e_nmd[slot] = v;
       };
-      const bool has_nmd = (EP == JG_EP_GENERIC || EP == JG_EP_RUNTIME) ? a.nmd_out != nullptr : (EP & (JG_EP_NMD1 | JG_EP_NMD2)) != 0;
+      const bool has_nmd = (EP == JG_EP_GENERIC || EP == JG_EP_RUNTIME) ? e_nmd != nullptr : (EP & (JG_EP_NMD1 | JG_EP_NMD2)) != 0;
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn) {
 #pragma unroll
@@ -1257,15 +1373,31 @@ void conv_f16x3_kernel(ConvHArgs a) {
           }
         }
       }
-      if (a.pool_out != nullptr) {
+      if constexpr (OPOS) {          // what only the stores need is read here, behind the blocks' arithmetic, so that
+                                     // it is not another handful of live scalars while the blocks are worked
+        typedef const __attribute__((address_space(4))) ConvHArgs *KArgs;
+        KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        e_y = ka->y;
+        e_pool = ka->pool_out;
+        e_overflow = ka->overflow;
+      }
+      if (e_pool != nullptr) {
         // fused masked global max pool (layers.py:496-538): the block outputs are not stored at all; each
         // wave reduces its 128 positions to one partial row, pool_final takes the max over a window's rows
         float mkv[TM];
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm) {
-          int orow, mc;
-          const bool live = out_pos(cur[0], tm, orow, mc);
-          const unsigned char mb = a.mask_out != nullptr ? a.mask_out[(size_t)orow * a.L_out + mc] : (unsigned char)1;
+          bool live;
+          unsigned char mb;
+          if constexpr (OPOS) {
+            live = ((olive >> tm) & 1u) != 0u;
+            mb = o_maskbyte(tm);
+          } else {
+            int orow, mc;
+            live = out_pos(cur[0], tm, orow, mc);
+            mb = a.mask_out != nullptr ? a.mask_out[(size_t)orow * a.L_out + mc] : (unsigned char)1;
+          }
           mkv[tm] = (live && mb != 0) ? 1.f : 0.f;
         }
 #pragma unroll
@@ -1280,16 +1412,33 @@ void conv_f16x3_kernel(ConvHArgs a) {
           const float v = lane_reduce(pa, [](float x, float y) { return fmaxf(x, y); });
           int ch;
           const size_t slot = reduced_slot(cur[0], tn, ch);
-          if (i < 16 && cur[0].valid && ch < a.cout) a.pool_out[slot] = v;
+          if (i < 16 && cur[0].valid && ch < a.cout) e_pool[slot] = v;
+        }
+      } else if constexpr (OPOS) {
+        auto store_tile = [&](bool f16s) {
+#pragma unroll
+          for (int tm = 0; tm < TM; ++tm) {
+            if (!((olive >> tm) & 1u)) continue;
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn) store_block(acc[tm][tn], cur[0], tm, tn, f16s);
+          }
+        };
+        if (!(e_dbg & 64)) {
+          if (e_f16s) {
+            store_tile(true);
+          } else {
+            f32_base = reinterpret_cast<char *>(const_cast<void *>(e_y)) + (o_mrow * (size_t)HN + (size_t)(wn * 64)) * 4u;
+            store_tile(false);
+          }
         }
       } else {
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm) {
 #pragma unroll
-          for (int tn = 0; tn < TN; ++tn) store_block(acc[tm][tn], cur[0], tm, tn);
+          for (int tn = 0; tn < TN; ++tn) store_block(acc[tm][tn], cur[0], tm, tn, false);
         }
       }
-      if ((!(vmax <= 65000.0f) || vnan) && a.overflow != nullptr && a.dbg == 0) atomicOr(a.overflow, 1);
+      if ((!(vmax <= 65000.0f) || vnan) && e_overflow != nullptr && e_dbg == 0) atomicOr(e_overflow, 1);
       JG_PRIO_MAIN();
     }
     if constexpr (!PIPE) zero_acc();          // (the pipelined loop starts every tile's accumulators from C = 0)
