@@ -674,6 +674,8 @@ static int prepare_small(jg_model *m, const float *weights) {
       if (!(st < c.n_stages && c.stages[st].kind == JG_ST_ACT && c.stages[st].arg == JG_ACT_GELU_TANH)) { ok = false; break; }
       ++st;
       ly.aff2 = 1;
+      // (the first layer's accumulators come out of the table phase and its epilogue has no second affine: jg_small.hip)
+      if (q == 0) { ok = false; break; }
     }
     if (st < c.n_stages && c.stages[st].kind == JG_ST_NMD && st == c.n_stages - 1) {
       // a tap behind the layer's last stage: masked channel sums of the layer's output, finished by the NMD_FINAL op

@@ -10,9 +10,11 @@ A restatement of the op semantics ``include/jaeger_hip.h`` documents, evaluated 
   kernel's output is compared with an exact evaluation of that op alone.
 
 Tensors are laid out like the engine's: activations (rows, frames, L, C), masks (rows, frames, L) (0 / 1), vectors
-(rows, width); rows = program rows (windows, or windows x strands).  A conv's result also carries its magnitude ``M``:
+(rows, width); rows = program rows (windows, or windows x strands).  A conv's result also carries its magnitude ``M``
+(a pool's or an NMD finish's: the same pool / mean of its input's magnitude under the same mask, plus ``|moving mean|``):
 the same linear part evaluated on ``|x * mask|`` and ``|W|``, plus ``|bias|``, through ``|BN scale|`` (plus ``|scale * mean|
-+ |beta|``), plus ``|residual|``, times the Lipschitz constant of every activation on the way - the scale of what the
++ |beta|``), plus ``|residual|``, times the Lipschitz constant of every activation on the way (plus ``|f(0)|``: the sigmoid's
+1 / 2) - the scale of what the
 kernel summed, which the error bounds are written in.
 """
 
@@ -43,7 +45,7 @@ def act(kind: int, x: np.ndarray) -> np.ndarray:
     if kind == ACT_NONE:
         return x
     if kind == ACT_GELU_TANH:
-        return 0.5 * x * (1.0 + np.tanh(0.7978845608028654 * (x + 0.044715 * x ** 3)))
+        return 0.5 * x * (1.0 + np.tanh(0.7978845608028654 * (x + 0.044715 * (x * x * x))))
     if kind == ACT_GELU_ERF:
         return 0.5 * x * torch.erfc(torch.from_numpy(-x * 0.7071067811865476)).numpy()
     if kind == ACT_RELU:
@@ -70,12 +72,17 @@ def shifted_sum(x: np.ndarray, w: np.ndarray, stride: int, dil: int, pad_left: i
     k = w.shape[0]
     l_in = x.shape[-2]
     y = np.zeros(x.shape[:-2] + (l_out, w.shape[2]))
-    m = np.arange(l_out)
     for t in range(k):
-        src = m * stride + t * dil - pad_left
-        ok = (src >= 0) & (src < l_in)
-        if ok.any():
-            y[..., ok, :] += x[..., src[ok], :] @ w[t]
+        # outputs m with 0 <= m s + t d - pad_left < l_in: a contiguous range (slices and one 2-D product per tap: index
+        # arrays and a batched product run ten times slower on tensors of this size; torch's float64 product: numpy's
+        # BLAS takes milliseconds to start its threads for a product this small)
+        off = t * dil - pad_left
+        m0 = max(0, -(off // stride))
+        m1 = min(l_out, (l_in - 1 - off) // stride + 1)
+        if m1 > m0:
+            xs = x[..., m0 * stride + off:(m1 - 1) * stride + off + 1:stride, :]
+            prod = torch.from_numpy(xs.reshape(-1, xs.shape[-1])) @ torch.from_numpy(np.ascontiguousarray(w[t]))
+            y[..., m0:m1, :] += prod.numpy().reshape(xs.shape[:-1] + (w.shape[2],))
     return y
 
 
@@ -85,6 +92,7 @@ class OpOut:
     M: np.ndarray | None = None           # magnitude of a conv / element-wise result (same shape as out)
     mask: np.ndarray | None = None        # EMBED: the mask it writes
     taps: dict = field(default_factory=dict)   # NMD partial slot -> the tensor the ST_NMD stage saw
+    taps_M: dict = field(default_factory=dict)  # NMD partial slot -> that tensor's magnitude
 
 
 @dataclass
@@ -96,6 +104,7 @@ class State:
     part: dict = field(default_factory=dict)
     vec: dict = field(default_factory=dict)
     M: dict = field(default_factory=dict)     # slot -> magnitude of an activation that is itself a reference (not a readback)
+    part_M: dict = field(default_factory=dict)   # NMD partial slot -> magnitude of the tapped tensor (default: its absolute value)
 
 
 def _blob(program, off: int, n: int) -> np.ndarray:
@@ -129,7 +138,7 @@ def conv_input(program, op, state: State) -> np.ndarray:
 def _stages(program, op, v: np.ndarray, M: np.ndarray, state: State, first: int = 0):
     c = op.cout
     out_mask = _mask_of(state, op.out_mask)
-    taps = {}
+    taps, taps_m = {}, {}
     for s in range(first, op.n_stages):
         st = op.stages[s]
         if st.kind == ST_BIAS:
@@ -150,9 +159,10 @@ def _stages(program, op, v: np.ndarray, M: np.ndarray, state: State, first: int 
             r = np.asarray(state.act[st.arg], np.float64)
             v, M = v + r, M + state.M.get(st.arg, np.abs(r))
         elif st.kind == ST_ACT:
-            v, M = act(st.arg, v), M * LIPSCHITZ[st.arg]
+            v, M = act(st.arg, v), M * LIPSCHITZ[st.arg] + (0.5 if st.arg == ACT_SIGMOID else 0.0)    # (+ |f(0)|)
         elif st.kind == ST_NMD:
             taps[st.arg] = v.copy()
+            taps_m[st.arg] = M.copy()
         elif st.kind == ST_MASKMUL:
             if out_mask is not None:
                 v, M = v * out_mask[..., None], M * out_mask[..., None]
@@ -169,7 +179,7 @@ def _stages(program, op, v: np.ndarray, M: np.ndarray, state: State, first: int 
                 v, M = v * out_mask[..., None], M * out_mask[..., None]
         else:
             raise ValueError(f"stage kind {st.kind}")
-    return v, M, taps
+    return v, M, (taps, taps_m)
 
 
 def mask_rule(m_in: np.ndarray, k: int, stride: int, dil: int, padding: int, mode: int) -> np.ndarray:
@@ -223,12 +233,12 @@ def run_op(program, i: int, inputs: State) -> OpOut:
             m = _mask_of(st, op.in_mask)
             ax = st.M[op.in_buf] if m is None else st.M[op.in_buf] * m[..., None]
         M = shifted_sum(ax, np.abs(w), op.stride, op.dilation, pl, lo)
-        y, M, taps = _stages(program, op, y, M, st)
-        return OpOut(y, M, taps=taps)
+        y, M, (taps, taps_m) = _stages(program, op, y, M, st)
+        return OpOut(y, M, taps=taps, taps_M=taps_m)
     if op.kind == OP_ELTWISE:
         x = np.asarray(st.act[op.in_buf], np.float64)
-        y, M, taps = _stages(program, op, x, np.abs(x), st)
-        return OpOut(y, M, taps=taps)
+        y, M, (taps, taps_m) = _stages(program, op, x, np.abs(x), st)
+        return OpOut(y, M, taps=taps, taps_M=taps_m)
     if op.kind == OP_MASK:
         m = _mask_of(st, op.in_mask)
         return OpOut(mask_rule(m, op.k, op.stride, op.dilation, op.padding, op.mask_mode))
@@ -246,25 +256,33 @@ def run_op(program, i: int, inputs: State) -> OpOut:
         x = np.asarray(st.act[op.in_buf], np.float64)
         return OpOut(x.sum(axis=1, keepdims=True), np.abs(x).sum(axis=1, keepdims=True))
     if op.kind == OP_POOL:
+        # M: the same pool of the input's magnitude under the same mask (|max a - max b| <= max |a - b|)
         x = np.asarray(st.act[op.in_buf], np.float64)
+        ax = np.asarray(st.M.get(op.in_buf, np.abs(x)), np.float64)
         x = x.reshape(x.shape[0], -1, x.shape[-1])
+        ax = ax.reshape(x.shape)
         m = _mask_of(st, op.in_mask)
         if m is None or op.arg == POOL_MAX_NOMASK:
-            return OpOut(x.mean(axis=1) if op.arg == POOL_AVG else x.max(axis=1))
+            return OpOut(x.mean(axis=1), ax.mean(axis=1)) if op.arg == POOL_AVG else OpOut(x.max(axis=1), ax.max(axis=1))
         m = m.reshape(m.shape[0], -1, 1)
         if op.arg == POOL_AVG:
-            return OpOut((x * m).sum(axis=1) / np.maximum(m.sum(axis=1), 1e-7))
+            cnt = np.maximum(m.sum(axis=1), 1e-7)
+            return OpOut((x * m).sum(axis=1) / cnt, (ax * m).sum(axis=1) / cnt)
+        some = m.max(axis=1) > 0
         pooled = np.where(m > 0, x, -1.0e9).max(axis=1)
-        return OpOut(np.where(m.max(axis=1) > 0, pooled, 0.0))
+        return OpOut(np.where(some, pooled, 0.0), np.where(some, (ax * m).max(axis=1), 0.0))
     if op.kind == OP_NMD_FINAL:
         part = np.asarray(st.part[op.arg], np.float64)
+        apart = np.asarray(st.part_M.get(op.arg, np.abs(part)), np.float64)
         part = part.reshape(part.shape[0], -1, part.shape[-1])
+        apart = apart.reshape(part.shape)
         mm = _blob(program, op.b_off, op.cout)
         m = _mask_of(st, op.in_mask)
         if m is None:
-            return OpOut(part.mean(axis=1) - mm)
+            return OpOut(part.mean(axis=1) - mm, apart.mean(axis=1) + np.abs(mm))
         m = m.reshape(m.shape[0], -1, 1)
-        return OpOut((part * m).sum(axis=1) / (m.sum(axis=1) + float(np.float32(op.f0))) - mm)
+        cnt = m.sum(axis=1) + float(np.float32(op.f0))
+        return OpOut((part * m).sum(axis=1) / cnt - mm, (apart * m).sum(axis=1) / cnt + np.abs(mm))
     if op.kind == OP_DENSE:
         v = np.asarray(st.vec[op.in_vec], np.float64)[:, :op.cin]
         y = v @ _blob(program, op.w_off, op.cin * op.cout).reshape(op.cin, op.cout)
@@ -311,6 +329,7 @@ def apply(program, i: int, state: State, res: OpOut) -> None:
         if res.mask is not None:
             state.mask[op.out_mask] = res.mask
         state.part.update(res.taps)
+        state.part_M.update(res.taps_M)
     elif op.kind in (OP_POOL, OP_NMD_FINAL, OP_DENSE, OP_OODSIG, OP_VECMAX):
         _put_vec(state, op.out_vec, op.vec_off, res.out)
 
