@@ -60,6 +60,13 @@ typedef enum {
                           exceeds 256.  w_off >= 0: + postab[position in the row] (k rows x cout floats: the rows of
                           SinusoidalPositionEmbedding, use_positional_embeddings, builder.py:886-892) - then also for one-byte ids */
   JG_OP_VECMAX = 12,   /* NMDMerge(mode="max") (nnlib/v2/nmd.py:150-152): out_vec[vec_off + c] = max over g < k of in_vec[g * cout + c] */
+  JG_OP_FRAMEATTN = 13, /* CrossFrameAttention (nnlib/v2/layers.py:2283-2384) as one launch: in_buf -> out_buf, f32 rows (6, L, C) per
+                          window; cin = cout = C channels, k = heads (key_dim C / k), arg = feed-forward width (0 = use_ffn false),
+                          f0 = epsilon of the two layer norms; w_off = the packed weights (layer-norm gamma / beta and the
+                          query's 1 / sqrt(key_dim) folded in on the host): wqkv [3][C][C] | bqkv [3][C] | wo [C][C] | bo [C] and,
+                          with arg > 0, w1 [C][arg] | b1 [arg] | w2 [arg][C] | b2 [C]; out_mask = JG_BUF_NONE (the layer does not
+                          set supports_masking: nothing behind it sees a mask); stages: bias / batch norm / unmasked DyT / activation.
+                          C 32 or 64, key_dim 4 .. 64, arg <= 256: jg_model_create refuses other sizes with the reason */
   JG_OP_STRANDS = 10   /* a branched (shared-weight) model over the k strands of a nucleotide input: every strand is a
                           program row of its own (ids (W, k, L), one frame per row); arg = how the strands' predictions
                           merge (jg_merge_kind); the embedding output is their average.  builder.py:1195-1266, :776-791 */
@@ -225,6 +232,7 @@ int64_t jg_model_get_stat(const jg_model *m, int key);
  *   kernel, pool / dense / vector ops; jg_predict_windows refuses to run while a tap is set.
  * JG_MSTAT_TAP_VARIANT: JG_TAP_* bits of the tapped launches of the last jg_forward call (OR over its launch groups;
  * still readable after the tap is turned off). */
+/* (a frame-attention op reports JG_TAP_EXACT_F32: its one arithmetic; its one layout, f32 rows, has no bit) */
 enum { JG_TAP_F16S = 1, JG_TAP_PHASE_SPLIT = 2, JG_TAP_WINDOW_PACKED = 4, JG_TAP_TABLE_LOOKUP = 8, JG_TAP_NARROW = 16,
        JG_TAP_EXACT_F32 = 32, JG_TAP_FUSED_RESBLOCK = 64 };
 int jg_model_tap_shape(const jg_model *m, int op, int32_t l, int64_t shape[4]);
@@ -283,7 +291,7 @@ int jg_predict_windows(jg_model *m, const uint8_t *bases, int64_t n_bases, int b
 
 /* widths of the named outputs: which = 0 prediction, 1 reliability, 2 embedding, 3 nmd */
 int jg_model_vec_width(const jg_model *m, int which);
-/* algorithmic conv FLOPs of one window at l codons per frame */
+/* algorithmic FLOPs of one window at l codons per frame: the convolutions and the dense products of frame-attention ops */
 double jg_model_flops_per_window(const jg_model *m, int32_t l);
 
 /* ---- device memory helpers (so callers need no other GPU runtime) ------- */
@@ -301,8 +309,10 @@ int jg_profile_enable(jg_engine *e, int on);
 int jg_profile_read(jg_engine *e, double *conv_ms, int64_t *conv_launches, double *conv_flops);
 /* the same accumulators split by kernel family: split-f16 matrix-core convs, exact-f32 matrix-core convs, the
  * first layer's table-lookup kernel (no matrix cores: its "FLOPs" are the algorithmic ones of the conv it replaces),
- * and the fused small-window network kernel */
-enum { JG_PROF_MFMA_F16X3 = 0, JG_PROF_MFMA_F32 = 1, JG_PROF_TABLE = 2, JG_PROF_FUSED_SMALL = 3 };
+ * the fused small-window network kernel, and the frame-attention kernel (FLOPs of its four dense products) */
+enum { JG_PROF_MFMA_F16X3 = 0, JG_PROF_MFMA_F32 = 1, JG_PROF_TABLE = 2, JG_PROF_FUSED_SMALL = 3, JG_PROF_FRAMEATTN = 4,
+       JG_PROF_FRAMEATTN_CVT = 5 /* the F16S -> f32 layout conversion a split-f16 program queues in front of a frame-attention op */,
+       JG_PROF_CLASSES = 6 };
 int jg_profile_read_class(jg_engine *e, int cls, double *ms, int64_t *launches, double *flops);
 
 /* Box calibration (bench.py's `box` object; no counterpart in the reference): about `seconds` (0 < seconds <= 30) of

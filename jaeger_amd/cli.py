@@ -100,6 +100,11 @@ def verify_model_cmd(graph_dir, project, legacy):
     if not legacy and project is None:
         raise click.UsageError("pass --project <name>_project.yaml or --legacy")
     plan = None if legacy else build_plan(yaml.safe_load(open(project).read())["model"])
+    from .verify import refuse_attention
+    try:
+        refuse_attention(plan)
+    except ValueError as e:                    # (UnsupportedLayer: a plan the check does not cover)
+        raise click.ClickException(str(e))
     click.echo(report(graph_dir, plan, legacy))
     sys.exit(1 if verify_model(graph_dir, plan, legacy) else 0)
 

@@ -13,6 +13,7 @@
 #include "jg_small.h"
 #include "jg_resblock64.h"
 #include "jg_vecmax.h"
+#include "jg_frameattn.h"
 
 static thread_local char g_err[1024] = "";
 
@@ -258,7 +259,7 @@ extern "C" int jg_profile_enable(jg_engine *e, int on) {
   e->conv_ms = 0.0;
   e->conv_flops = 0.0;
   e->conv_launches = 0;
-  for (int i = 0; i < 4; ++i) { e->cls_ms[i] = 0.0; e->cls_flops[i] = 0.0; e->cls_launches[i] = 0; }
+  for (int i = 0; i < JG_PROF_CLASSES; ++i) { e->cls_ms[i] = 0.0; e->cls_flops[i] = 0.0; e->cls_launches[i] = 0; }
   return JG_OK;
 }
 
@@ -270,9 +271,10 @@ static int drain_profile(jg_engine *e) {
     e->conv_ms += ms;
     e->conv_flops += p.flops;
     e->conv_launches += 1;
-    e->cls_ms[p.cls & 3] += ms;
-    e->cls_flops[p.cls & 3] += p.flops;
-    e->cls_launches[p.cls & 3] += 1;
+    const int cls = p.cls >= 0 && p.cls < JG_PROF_CLASSES ? p.cls : 0;
+    e->cls_ms[cls] += ms;
+    e->cls_flops[cls] += p.flops;
+    e->cls_launches[cls] += 1;
     e->pool.push_back(p.a);
     e->pool.push_back(p.b);
   }
@@ -293,7 +295,7 @@ extern "C" int jg_profile_read(jg_engine *e, double *conv_ms, int64_t *conv_laun
 }
 
 extern "C" int jg_profile_read_class(jg_engine *e, int cls, double *ms, int64_t *launches, double *flops) {
-  JG_REQUIRE(e != nullptr && cls >= 0 && cls < 4, JG_ERR_INVALID, "jg_profile_read_class: bad arguments");
+  JG_REQUIRE(e != nullptr && cls >= 0 && cls < JG_PROF_CLASSES, JG_ERR_INVALID, "jg_profile_read_class: bad arguments");
   JG_HIP(hipSetDevice(e->dev));
   int rc = drain_profile(e);
   if (rc != JG_OK) return rc;
@@ -342,7 +344,7 @@ static int validate_program(const jg_model *m) {
     auto slot_ok = [](int s, bool allow_ids) {
       return (s >= 0 && s < JG_MAX_BUFS) || s == JG_BUF_NONE || (allow_ids && s == JG_BUF_IDS);
     };
-    JG_REQUIRE(op.kind >= JG_OP_CONV && op.kind <= JG_OP_VECMAX, JG_ERR_INVALID,
+    JG_REQUIRE(op.kind >= JG_OP_CONV && op.kind <= JG_OP_FRAMEATTN, JG_ERR_INVALID,
                "op %zu: unknown kind %d", i, op.kind);
     if (op.kind == JG_OP_VECMAX)
       JG_REQUIRE(op.in_vec >= 0 && op.out_vec >= 0 && op.in_vec != op.out_vec && op.k >= 1 && op.cout >= 1 && op.vec_off >= 0,
@@ -379,6 +381,23 @@ static int validate_program(const jg_model *m) {
     } else if (!m->ops.empty() && m->ops[0].kind == JG_OP_EMBED) {
       JG_REQUIRE(op.in_buf != JG_BUF_IDS && op.in_mask != JG_BUF_IDS, JG_ERR_INVALID,
                  "op %zu: reads the id tensor directly in a program that opens with an embedding op (its buffer and mask take the tensor's place)", i);
+    }
+    if (op.kind == JG_OP_FRAMEATTN) {
+      // cin = cout = channels, k = heads, arg = feed-forward width (0: no feed-forward half), f0 = the layer norms' epsilon
+      JG_REQUIRE(op.in_buf >= 0 && op.out_buf >= 0 && op.cin == op.cout && op.out_mask == JG_BUF_NONE && op.f0 > 0.f,
+                 JG_ERR_INVALID, "op %zu: a frame-attention op reads and writes an activation slot of cin = cout channels and leaves no mask", i);
+      char why[160];
+      JG_REQUIRE(jg_frameattn_supports(op.cin, op.k, op.arg, why, sizeof(why)), JG_ERR_UNSUPPORTED,
+                 "op %zu: frame attention with %s", i, why);
+      JG_REQUIRE(m->ops.back().kind != JG_OP_STRANDS, JG_ERR_UNSUPPORTED,
+                 "op %zu: frame attention needs the six frames of a translated window (not a strand program)", i);
+      JG_REQUIRE(off_ok(op.w_off, jg_frameattn_blob_floats(op.cin, op.arg)), JG_ERR_INVALID,
+                 "op %zu: frame-attention weights outside the weight blob", i);
+      for (int s = 0; s < op.n_stages; ++s) {
+        const int kd = op.stages[s].kind;
+        JG_REQUIRE(kd == JG_ST_BIAS || kd == JG_ST_BN || kd == JG_ST_ACT || (kd == JG_ST_DYT && op.stages[s].arg == 0), JG_ERR_UNSUPPORTED,
+                   "op %zu stage %d: only bias / batch norm / unmasked DyT / activation stages fuse behind frame attention (kind %d)", i, s, kd);
+      }
     }
     if (op.kind == JG_OP_DENSE) {
       JG_REQUIRE(off_ok(op.w_off, (int64_t)op.cin * op.cout), JG_ERR_INVALID,
@@ -506,6 +525,14 @@ static int plan_shapes(jg_model *m, int l, int64_t act_elems[JG_MAX_BUFS],
             nmd_elems[op.stages[s].arg] = std::max<int64_t>(nmd_elems[op.stages[s].arg], (int64_t)in.frames * tiles * in.C);
           }
       } break;
+      case JG_OP_FRAMEATTN: {
+        const Shape in = sh[op.in_buf];
+        JG_REQUIRE(in.C == op.cin && in.frames == 6, JG_ERR_INVALID,
+                   "op %zu: frame attention over %d channels expects (6, L, %d) rows, input is (%d, L, %d)", i, op.cin, op.cin, in.frames, in.C);
+        sh[op.out_buf] = in;
+        act_elems[op.out_buf] = std::max<int64_t>(act_elems[op.out_buf], (int64_t)in.frames * (in.L + (in.L & 1)) * in.C);
+        fl += 2.0 * (4.0 * op.cin * op.cin + 2.0 * op.cin * op.arg) * (double)in.frames * in.L;   // the four dense products
+      } break;
       case JG_OP_MAXPOOL1D: {
         const Shape in = sh[op.in_buf];
         const int lo = in.L / 2;
@@ -620,7 +647,7 @@ static int prepare_small(jg_model *m, const float *weights) {
   for (size_t i = (size_t)pool_op + 1; i < m->ops.size(); ++i) {
     const int k = m->ops[i].kind;
     if (k == JG_OP_CONV || k == JG_OP_MASK || k == JG_OP_POOL || k == JG_OP_ELTWISE || k == JG_OP_MAXPOOL1D ||
-        k == JG_OP_FRAMESUM || k == JG_OP_NMD_FINAL)
+        k == JG_OP_FRAMESUM || k == JG_OP_NMD_FINAL || k == JG_OP_FRAMEATTN)
       return JG_OK;
   }
   JgSmallNet *sn = new JgSmallNet();
@@ -1165,7 +1192,7 @@ static int prepare_f16(jg_model *m, const float *weights) {
   auto reads = [&](size_t j, int buf) {
     const jg_op &o = m->ops[j];
     if ((o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-         o.kind == JG_OP_POOL || o.kind == JG_OP_NMD_FINAL) && o.in_buf == buf)
+         o.kind == JG_OP_POOL || o.kind == JG_OP_NMD_FINAL || o.kind == JG_OP_FRAMEATTN) && o.in_buf == buf)
       return o.kind != JG_OP_NMD_FINAL;               // (NMD_FINAL only takes the slot's shape)
     if (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE)
       for (int q = 0; q < o.n_stages; ++q)
@@ -1175,7 +1202,7 @@ static int prepare_f16(jg_model *m, const float *weights) {
   auto writes = [&](size_t j, int buf) {
     const jg_op &o = m->ops[j];
     return (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-            o.kind == JG_OP_EMBED) &&
+            o.kind == JG_OP_EMBED || o.kind == JG_OP_FRAMEATTN) &&
            o.out_buf == buf;
   };
   bool cvt_overflow = false;
@@ -1238,6 +1265,10 @@ static int prepare_f16(jg_model *m, const float *weights) {
           if (op.stages[q].kind == JG_ST_ADD) need(i, op.stages[q].arg, true);
         is_f32[op.out_buf] = true;
         break;
+      case JG_OP_FRAMEATTN:                             // f32 rows in and out: an F16S producer is converted in front of it
+        need(i, op.in_buf, true);
+        is_f32[op.out_buf] = true;
+        break;
       case JG_OP_MAXPOOL1D:
         hp.pool_f16s = op.in_buf >= 0 && !is_f32[op.in_buf];
         is_f32[op.out_buf] = !hp.pool_f16s;
@@ -1278,7 +1309,7 @@ static int plan_phase_split(jg_model *m, const float *weights) {
   auto reads_buf = [&](size_t j, int buf) {
     const jg_op &o = m->ops[j];
     if ((o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-         o.kind == JG_OP_POOL || o.kind == JG_OP_NMD_FINAL) && o.in_buf == buf)
+         o.kind == JG_OP_POOL || o.kind == JG_OP_NMD_FINAL || o.kind == JG_OP_FRAMEATTN) && o.in_buf == buf)
       return true;
     if (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE)
       for (int q = 0; q < o.n_stages; ++q)
@@ -1288,7 +1319,7 @@ static int plan_phase_split(jg_model *m, const float *weights) {
   auto writes_buf = [&](size_t j, int buf) {
     const jg_op &o = m->ops[j];
     return (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-            o.kind == JG_OP_EMBED) &&
+            o.kind == JG_OP_EMBED || o.kind == JG_OP_FRAMEATTN) &&
            o.out_buf == buf;
   };
   for (size_t p = 0; p < n; ++p) {
@@ -1382,7 +1413,7 @@ static int plan_resblocks(jg_model *m, const float *weights) {
   auto reads_buf = [&](size_t j, int buf) {
     const jg_op &o = m->ops[j];
     if ((o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-         o.kind == JG_OP_POOL || o.kind == JG_OP_NMD_FINAL) && o.in_buf == buf)
+         o.kind == JG_OP_POOL || o.kind == JG_OP_NMD_FINAL || o.kind == JG_OP_FRAMEATTN) && o.in_buf == buf)
       return true;
     if (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE)
       for (int q = 0; q < o.n_stages; ++q)
@@ -1392,7 +1423,7 @@ static int plan_resblocks(jg_model *m, const float *weights) {
   auto writes_buf = [&](size_t j, int buf) {
     const jg_op &o = m->ops[j];
     return (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-            o.kind == JG_OP_EMBED) &&
+            o.kind == JG_OP_EMBED || o.kind == JG_OP_FRAMEATTN) &&
            o.out_buf == buf;
   };
   // bias / batch-norm stages in front of the first other stage, folded with the weights' un-scale (as prepare_f16 does)
@@ -1510,6 +1541,13 @@ extern "C" int jg_model_describe(const jg_model *m, char *buf, int64_t cap) {
   char line[512];
   for (size_t i = 0; i < m->ops.size(); ++i) {
     const jg_op &op = m->ops[i];
+    if (op.kind == JG_OP_FRAMEATTN) {
+      snprintf(line, sizeof(line), "op %zu: frame attention c=%d heads=%d key_dim=%d ff=%d -> one launch, exact-f32 matrix cores, f32 rows%s\n",
+               i, op.cin, op.k, op.cin / op.k, op.arg,
+               (m->f16_eligible && m->hprep[i].n_cvt > 0) ? " (F16S -> f32 conversion in front)" : "");
+      out += line;
+      continue;
+    }
     if (op.kind != JG_OP_CONV) continue;
     const ConvHPrep &hp = m->hprep[i];
     const char *where = m->small != nullptr ? "fused small-window kernel"
@@ -1758,7 +1796,7 @@ static int grow(T **p, int64_t *cap, int64_t need_bytes) {
 static const char *tap_refusal(const jg_model *m, size_t i, char *why, size_t cap) {
   const jg_op &op = m->ops[i];
   if (op.kind != JG_OP_CONV && op.kind != JG_OP_MASK && op.kind != JG_OP_ELTWISE && op.kind != JG_OP_EMBED &&
-      op.kind != JG_OP_MAXPOOL1D && op.kind != JG_OP_FRAMESUM) {
+      op.kind != JG_OP_MAXPOOL1D && op.kind != JG_OP_FRAMESUM && op.kind != JG_OP_FRAMEATTN) {
     snprintf(why, cap, "op %zu (kind %d) writes a vector or nothing - pool, dense and vector results are outputs already", i, op.kind);
     return why;
   }
@@ -1813,6 +1851,7 @@ static int tap_copy(jg_model *m, size_t i, const Shape *sh, const int *mlen, int
     if (f16_conv && hp.d_lut != nullptr) v |= JG_TAP_TABLE_LOOKUP;
     if (f16_conv && hp.cw != 128) v |= JG_TAP_NARROW;
   }
+  if (op.kind == JG_OP_FRAMEATTN) v |= JG_TAP_EXACT_F32;      // one arithmetic (exact-f32 matrix cores), one layout (f32 rows)
   m->tap_variant |= v;
   float *out = reinterpret_cast<float *>(dst + m->tap_row0 * per_row);
   if (!f16s) {
@@ -1940,9 +1979,23 @@ static int run_chunk(jg_model *m, const uint8_t *d_ids, int nw, int l, hipStream
         const int slot = hq.cvt_slot[q];
         const Shape &t = sh[slot];
         const int64_t rows = (int64_t)nw * t.frames;
+        // (the conversion in front of a frame-attention op is timed as a class of its own: what a kernel variant that
+        // reads F16S directly would save)
+        const bool timed = e->profile && op.kind == JG_OP_FRAMEATTN;
+        ProfEvent pe;
+        if (timed) {
+          if ((rc = prof_event(e, &pe.a)) != JG_OK || (rc = prof_event(e, &pe.b)) != JG_OK) return rc;
+          pe.flops = 0.0;
+          pe.cls = JG_PROF_FRAMEATTN_CVT;
+          JG_HIP(hipEventRecord(pe.a, s));
+        }
         if (hq.cvt_to_f32[q]) rc = jg_launch_f16s_to_f32(reinterpret_cast<const uint4 *>(m->act[slot]), rows, t.L, t.C, m->cvt_scratch, s);
         else rc = jg_launch_f32_to_f16s(m->act[slot], rows, t.L, t.C, reinterpret_cast<uint4 *>(m->cvt_scratch), s, m->d_overflow);
         if (rc != JG_OK) return rc;
+        if (timed) {
+          JG_HIP(hipEventRecord(pe.b, s));
+          e->pending.push_back(pe);
+        }
         std::swap(m->act[slot], m->cvt_scratch);
         std::swap(m->act_cap[slot], m->cvt_cap);
       }
@@ -2228,6 +2281,31 @@ static int run_chunk(jg_model *m, const uint8_t *d_ids, int nw, int l, hipStream
           rc = jg_launch_layernorm(a, nw * in.frames, in.L, (in.L + jg_conv_tile_m(in.L) - 1) / jg_conv_tile_m(in.L), s);
         else
           rc = jg_launch_eltwise(a, s);
+        sh[op.out_buf] = in;
+      } break;
+      case JG_OP_FRAMEATTN: {
+        const Shape in = sh[op.in_buf];
+        JgFrameAttnArgs a;
+        memset(&a, 0, sizeof(a));
+        a.x = m->act[op.in_buf];
+        a.y = m->act[op.out_buf];
+        a.w = m->d_w + op.w_off;
+        a.n_win = nw; a.L = in.L; a.tiles = (in.L + 15) / 16;
+        a.C = op.cin; a.H = op.k; a.D = op.cin / op.k; a.F = op.arg;
+        a.eps = op.f0;
+        resolve_stages(m, op, a.st, &a.n_stages);
+        ProfEvent pe;
+        if (e->profile) {
+          if ((rc = prof_event(e, &pe.a)) != JG_OK || (rc = prof_event(e, &pe.b)) != JG_OK) return rc;
+          pe.flops = 2.0 * (4.0 * a.C * a.C + 2.0 * a.C * a.F) * 6.0 * (double)nw * in.L;
+          pe.cls = JG_PROF_FRAMEATTN;
+          JG_HIP(hipEventRecord(pe.a, s));
+        }
+        rc = jg_launch_frameattn(e, a, s);
+        if (e->profile && rc == JG_OK) {
+          JG_HIP(hipEventRecord(pe.b, s));
+          e->pending.push_back(pe);
+        }
         sh[op.out_buf] = in;
       } break;
       case JG_OP_MAXPOOL1D: {

@@ -185,8 +185,8 @@ struct jg_engine {
   std::vector<hipEvent_t> pool;   // recycled events
   double conv_ms = 0.0, conv_flops = 0.0;
   int64_t conv_launches = 0;
-  double cls_ms[4] = {}, cls_flops[4] = {};     // the same split by kernel family (JG_PROF_*)
-  int64_t cls_launches[4] = {};
+  double cls_ms[JG_PROF_CLASSES] = {}, cls_flops[JG_PROF_CLASSES] = {};     // the same split by kernel family (JG_PROF_*)
+  int64_t cls_launches[JG_PROF_CLASSES] = {};
   int n_cu = 256;
   int dust_on_copy = 1;           // JG_OPT_DUST_ON_COPY_STREAM: streamed spans are soft-masked on the copy stream (1) or in front of their encoder (0)
   int termini_exact = 0;          // JG_OPT_TERMINI_EXACT: every terminal-repeat alignment through the length / gap carrying kernel

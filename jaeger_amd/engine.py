@@ -193,7 +193,7 @@ class HipDevice:
         ms, n, fl = C.c_double(), C.c_int64(), C.c_double()
         L.check(self.lib.jg_profile_read(self.handle, C.byref(ms), C.byref(n), C.byref(fl)))
         out = {"conv_ms": ms.value, "conv_launches": n.value, "conv_flops": fl.value}
-        for cls, name in enumerate(("mfma_f16x3", "mfma_f32", "table", "fused_small")):
+        for cls, name in enumerate(("mfma_f16x3", "mfma_f32", "table", "fused_small", "frame_attn", "frame_attn_cvt")):
             L.check(self.lib.jg_profile_read_class(self.handle, cls, C.byref(ms), C.byref(n), C.byref(fl)))
             out[name] = {"ms": ms.value, "launches": n.value, "flops": fl.value}
         return out

@@ -93,6 +93,38 @@ class Dense:
 
 
 @dataclass
+class FrameAttn:
+    """One CrossFrameAttention layer (layers.py:2283-2384): at every position the six frames are six tokens of
+    ``channels``: pre-LN (eps 1e-6, :2321-2323) -> MultiHeadAttention(num_heads, key_dim = channels // num_heads,
+    :2324-2330) over the frames -> residual (:2367); with ``use_ffn`` LN -> Dense(ff_dim, gelu) -> Dense(channels) ->
+    residual (:2370-2376).  The layer does not set supports_masking: no mask leaves it."""
+    name: str
+    channels: int
+    heads: int
+    key_dim: int
+    ff_dim: int
+    use_ffn: bool = True           # layers.py:2310
+
+
+#: what the frame-attention kernel (csrc/jg_frameattn.hip) covers
+FRAMEATTN_CHANNELS = (32, 64)
+FRAMEATTN_KEY_DIMS = (4, 8, 16, 32, 64)
+FRAMEATTN_MAX_FF = 256
+
+
+def frame_attn_limit(channels: int, heads: int, ff_dim: int) -> str | None:
+    """Why the frame-attention kernel cannot run this size, or None."""
+    if channels not in FRAMEATTN_CHANNELS:
+        return f"embed_dim {channels} (the kernel covers {' / '.join(map(str, FRAMEATTN_CHANNELS))} channels)"
+    if heads < 1 or channels % heads or channels // heads not in FRAMEATTN_KEY_DIMS:
+        return (f"num_heads {heads} at embed_dim {channels} (key_dim = embed_dim / num_heads must be one of "
+                f"{', '.join(map(str, FRAMEATTN_KEY_DIMS))})")
+    if ff_dim and (ff_dim % 16 or not 16 <= ff_dim <= FRAMEATTN_MAX_FF):
+        return f"feed_forward_dim {ff_dim} (a multiple of 16 up to {FRAMEATTN_MAX_FF})"
+    return None
+
+
+@dataclass
 class ModelPlan:
     vocab: int
     embedding_dim: int
@@ -147,8 +179,9 @@ def _norm(name: str, kind: str, channels: int, cfg: dict, use_masking: bool) -> 
 
 
 def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
-           nmd_dims: list[int] | None):
-    """builder.py:982-1158: walk one ``hidden_layers`` list."""
+           nmd_dims: list[int] | None, frames: int | None = None):
+    """builder.py:982-1158: walk one ``hidden_layers`` list.  ``frames``: the frame axis of the tensor the list runs on
+    (the representation learner of a translated model), None where there is none (heads, strand branches)."""
     out: list[Any] = []
     for i, layer in enumerate(layers):
         name = str(layer.get("name", "")).lower()
@@ -232,6 +265,25 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
             cin = int(cfg["units"])
         elif name == "dropout":
             continue                                            # identity at inference
+        elif name == "cross_frame_attention":
+            # builder.py:1155: CrossFrameAttention(**config) (embed_dim, num_heads, feed_forward_dim, dropout_rate, use_ffn);
+            # :1165-1166: previous_channels = embed_dim
+            if frames is None:
+                raise UnsupportedLayer(f"{p}: cross_frame_attention needs the (frames, length, channels) tensor of the "
+                                       "representation learner: not supported in a head or on a strand branch")
+            if frames != 6:
+                raise UnsupportedLayer(f"{p}: cross_frame_attention over {frames} frames (the kernel attends over the six "
+                                       "reading frames of a translated window)")
+            c, h = int(cfg["embed_dim"]), int(cfg["num_heads"])
+            use_ffn = bool(cfg.get("use_ffn", True))
+            f = int(cfg["feed_forward_dim"]) if use_ffn else 0
+            if c != cin:
+                raise UnsupportedLayer(f"{p}: embed_dim {c} != {cin} incoming channels (the layer's residual adds them, "
+                                       "layers.py:2367)")
+            why = frame_attn_limit(c, h, f)
+            if why is not None:
+                raise UnsupportedLayer(f"{p}: cross_frame_attention with {why}")
+            out.append(FrameAttn(p, c, h, c // h, f, use_ffn))
         else:
             raise UnsupportedLayer(
                 f"{p}: layer {name!r} is outside the Conv1D -> norm -> pool -> dense family "
@@ -313,7 +365,8 @@ def build_plan(model_cfg: dict) -> ModelPlan:
         sp["vocab_size"] = depth + 1                           # ids on the device: 0 = invalid / padding, id + 1 else
     nmd_dims: list[int] = []
     rep_cfg = model_cfg["representation_learner"]
-    rep, rep_c = _block(rep_cfg.get("hidden_layers", []), "rep", e, use_masking, nmd_dims)
+    frames = int((emb.get("input_shape") or [None])[0] or emb.get("frames", 6))   # the graph input is input_shape (builder.py:846)
+    rep, rep_c = _block(rep_cfg.get("hidden_layers", []), "rep", e, use_masking, nmd_dims, frames=frames)
     pooling = str(rep_cfg.get("pooling", "")).lower()
     pooling = {"masked_max": "max", "masked_average": "average"}.get(pooling, pooling)
     if pooling not in ("max", "average"):
@@ -466,12 +519,44 @@ def weight_shapes(plan: ModelPlan) -> dict[str, tuple]:
                 out[f"{layer.name}/kernel"] = (layer.cin, layer.units)
                 if layer.use_bias:
                     out[f"{layer.name}/bias"] = (layer.units,)
+            elif isinstance(layer, FrameAttn):
+                out.update(frame_attn_weight_shapes(layer))
         if seq is plan.rep and plan.nmd_merge_mode != "concat":                 # NMDMerge is built behind the rep block's layers
             for i, d in enumerate(plan.nmd_dims):
                 out[f"rep/nmd_merge/proj_{i}/kernel"] = (d, plan.nmd_merge_dim)
             if plan.nmd_merge_mode == "weighted":
                 out["rep/nmd_merge/layer_weights"] = (len(plan.nmd_dims),)
     return out
+
+
+def frame_attn_weight_shapes(a: FrameAttn) -> dict[str, tuple]:
+    """Keras variable shapes of one CrossFrameAttention layer: LayerNormalization gamma / beta (C); MultiHeadAttention
+    query / key / value EinsumDense kernels (C, H, D) with biases (H, D), attention_output kernel (H, D, C) with bias (C);
+    the two Dense layers of the feed-forward half."""
+    c, h, d, f = a.channels, a.heads, a.key_dim, a.ff_dim
+    out = {f"{a.name}/attn_norm/gamma": (c,), f"{a.name}/attn_norm/beta": (c,)}
+    for part in ("query", "key", "value"):
+        out[f"{a.name}/mha/{part}/kernel"] = (c, h, d)
+        out[f"{a.name}/mha/{part}/bias"] = (h, d)
+    out[f"{a.name}/mha/attention_output/kernel"] = (h, d, c)
+    out[f"{a.name}/mha/attention_output/bias"] = (c,)
+    if a.use_ffn:
+        out.update({f"{a.name}/ffn_norm/gamma": (c,), f"{a.name}/ffn_norm/beta": (c,),
+                    f"{a.name}/ffn_dense1/kernel": (c, f), f"{a.name}/ffn_dense1/bias": (f,),
+                    f"{a.name}/ffn_dense2/kernel": (f, c), f"{a.name}/ffn_dense2/bias": (c,)})
+    return out
+
+
+def frame_attn_flops_per_position(plan: ModelPlan) -> list[tuple[str, int, int]]:
+    """(name, FLOPs of the dense products, FLOPs of the score / softmax / context core) of every frame-attention layer,
+    per POSITION (six tokens): q/k/v and output projections 4 x 2 C^2, feed-forward 2 x 2 C F, per token; scores and
+    context 2 x 2 x 6 x 6 x C per position."""
+    rows = []
+    for layer in plan.rep:
+        if isinstance(layer, FrameAttn):
+            c, f = layer.channels, layer.ff_dim
+            rows.append((layer.name, 6 * (8 * c * c + 4 * c * f), 4 * 36 * c))
+    return rows
 
 
 def conv_flops_per_position(plan: ModelPlan) -> list[tuple[str, int, int, int, str, int]]:

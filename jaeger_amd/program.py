@@ -9,6 +9,8 @@ conv launches with epilogue stages:
   -> act [-> nmd -> norm -> activation that follow the stack]`` one conv op;
   optional ``conv3 -> bn3`` bypass one conv op
 * each conv with masking gets one tiny mask op (``layers.py:1226-1255``).
+* ``cross_frame_attention -> norm -> activation``             one frame-attention op (``layers.py:2283-2384``); no mask
+  leaves it
 
 Pure host logic (numpy + ctypes structs): unit-tested on CPU.
 """
@@ -20,7 +22,7 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 from . import _lib as L
-from .plan import Act, Conv, Dense, ModelPlan, Nmd, Norm, ResBlock, UnsupportedLayer, weight_shapes
+from .plan import Act, Conv, Dense, FrameAttn, ModelPlan, Nmd, Norm, ResBlock, UnsupportedLayer, weight_shapes
 
 _ACT_CODE = {None: L.ACT_NONE, "linear": L.ACT_NONE, "gelu": L.ACT_GELU_TANH, "gelu_erf": L.ACT_GELU_ERF,
              "relu": L.ACT_RELU, "tanh": L.ACT_TANH, "sigmoid": L.ACT_SIGMOID}
@@ -81,6 +83,36 @@ def pack_conv_kernel(kernel: np.ndarray) -> np.ndarray:
     return out
 
 
+FRAME_ATTN_EPSILON = 1e-6      # both LayerNormalization layers of CrossFrameAttention (layers.py:2321-2323, :2335-2337)
+
+
+def pack_frame_attn(a: FrameAttn, w: dict[str, np.ndarray]) -> np.ndarray:
+    """The weights of one CrossFrameAttention layer as the kernel reads them (csrc/jg_frameattn.hip), folded in float64:
+
+    * ``LN(x) @ W + b`` with ``LN(x) = n(x) * gamma + beta`` is ``n(x) @ (gamma[:, None] * W) + (beta @ W + b)``: the layer
+      norms' gamma / beta go into the q / k / v kernels and into ffn_dense1, the kernel normalises only;
+    * MultiHeadAttention multiplies the query by ``1 / sqrt(key_dim)`` behind its bias: into the query's kernel and bias.
+
+    Layout: wqkv [3][C][C] (q | k | v; input channel; h * D + d) | bqkv [3][C] | wo [C][C] (h * D + d; output channel) |
+    bo [C] and, with a feed-forward half, w1 [C][F] | b1 [F] | w2 [F][C] | b2 [C]."""
+    c, h, d = a.channels, a.heads, a.key_dim
+    f64 = lambda name: np.asarray(w[f"{a.name}/{name}"], np.float64)
+    g1, be1 = f64("attn_norm/gamma"), f64("attn_norm/beta")
+    parts_w, parts_b = [], []
+    for part, scale in (("query", 1.0 / np.sqrt(float(d))), ("key", 1.0), ("value", 1.0)):
+        kern = f64(f"mha/{part}/kernel").reshape(c, h * d)
+        bias = f64(f"mha/{part}/bias").reshape(h * d)
+        parts_w.append(g1[:, None] * kern * scale)
+        parts_b.append((be1 @ kern + bias) * scale)
+    out = [np.stack(parts_w), np.stack(parts_b), f64("mha/attention_output/kernel").reshape(h * d, c),
+           f64("mha/attention_output/bias")]
+    if a.use_ffn:
+        g2, be2 = f64("ffn_norm/gamma"), f64("ffn_norm/beta")
+        k1 = f64("ffn_dense1/kernel")
+        out += [g2[:, None] * k1, be2 @ k1 + f64("ffn_dense1/bias"), f64("ffn_dense2/kernel"), f64("ffn_dense2/bias")]
+    return np.concatenate([x.ravel() for x in out]).astype(np.float32)
+
+
 @dataclass
 class Program:
     ops: list            # list[L.JgOp]
@@ -105,7 +137,8 @@ class Program:
         for op in self.ops:
             st = "+".join(stk[op.stages[s].kind] for s in range(op.n_stages))
             rows.append(f"{kinds[op.kind][3:]:9s} in={op.in_buf} out={op.out_buf} m={op.in_mask}->{op.out_mask} "
-                        f"k={op.k} c={op.cin}->{op.cout} s={op.stride} d={op.dilation} [{st}]")
+                        f"k={op.k} c={op.cin}->{op.cout} s={op.stride} d={op.dilation} [{st}]"
+                        + (f" heads={op.k} ff={op.arg}" if op.kind == L.OP_FRAMEATTN else ""))
         return rows
 
 
@@ -171,11 +204,14 @@ class _Compiler:
                 stages, tail = stages[:j], stages[j:]
                 break
         self._emit_conv_op(c, in_buf, in_mask, stages, out_mask, out_buf)
+        self._emit_ln_tail(c.name, tail, out_mask, out_buf, c.filters)
+
+    def _emit_ln_tail(self, name: str, tail: list, out_mask: int, out_buf: int, channels: int):
         while tail:                                   # one op per LayerNorm (each leads its own op)
             nxt = next((j for j, st in enumerate(tail) if st.kind == L.ST_LN and j > 0), len(tail))
             if nxt > L.JG_MAX_STAGES:
-                raise UnsupportedLayer(f"{c.name}: more than {L.JG_MAX_STAGES} stages behind a layer norm")
-            op = self._op(L.OP_ELTWISE, in_buf=out_buf, out_buf=out_buf, out_mask=out_mask, cout=c.filters)
+                raise UnsupportedLayer(f"{name}: more than {L.JG_MAX_STAGES} stages behind a layer norm")
+            op = self._op(L.OP_ELTWISE, in_buf=out_buf, out_buf=out_buf, out_mask=out_mask, cout=channels)
             op.n_stages = nxt
             for j, st in enumerate(tail[:nxt]):
                 op.stages[j] = st
@@ -359,6 +395,34 @@ class _Compiler:
                         op.stages[j] = st
                     self.ops.append(op)
                 mask = mask2
+            elif isinstance(layer, FrameAttn):
+                if buf == L.JG_BUF_IDS:
+                    raise UnsupportedLayer(f"{layer.name}: cross_frame_attention directly on the embedding is not supported")
+                # CrossFrameAttention does not set supports_masking (layers.py:2283-2384): the norm / activation / pool / conv
+                # behind it see NO mask, and the values the network holds at masked positions flow on as they are.  The
+                # norm / activation that follow fuse into the op's store; a LayerNorm is cut off into its own op
+                stages: list = []
+                i, _ = self._fuse_tail(layers, i + 1, stages, L.JG_BUF_NONE, layer.channels, pending)
+                if pending:
+                    raise UnsupportedLayer(f"{layer.name}: an nmd tap directly behind cross_frame_attention is not supported "
+                                           "(the op's store carries no partial sums)")
+                tail = []
+                for j, st in enumerate(stages):
+                    if st.kind == L.ST_LN:
+                        stages, tail = stages[:j], stages[j:]
+                        break
+                out = self.bufs.take()
+                op = self._op(L.OP_FRAMEATTN, in_buf=buf, out_buf=out, in_mask=L.JG_BUF_NONE, out_mask=L.JG_BUF_NONE,
+                              k=layer.heads, cin=layer.channels, cout=layer.channels, arg=layer.ff_dim if layer.use_ffn else 0,
+                              f0=FRAME_ATTN_EPSILON, w_off=self.blob.add(pack_frame_attn(layer, self.w)))
+                op.n_stages = len(stages)
+                for j, st in enumerate(stages):
+                    op.stages[j] = st
+                self.ops.append(op)
+                self._emit_ln_tail(layer.name, tail, L.JG_BUF_NONE, out, layer.channels)
+                self.bufs.give(buf)
+                self.masks.give(mask)
+                buf, mask = out, L.JG_BUF_NONE
             elif isinstance(layer, Nmd):
                 raise UnsupportedLayer("an nmd layer must directly follow a conv or residual block")
             else:

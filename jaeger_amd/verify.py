@@ -48,8 +48,25 @@ def _legacy_expectations() -> dict:
             "gelu": "erf", "maxpool": 2}
 
 
+def refuse_attention(plan: ModelPlan | None) -> None:
+    """The census below counts what the conv family leaves in a serving graph (Conv2D nodes, batch-norm epsilons, the GELU
+    form, the mask comparisons).  What a CrossFrameAttention layer leaves there - Einsum nodes, two layer norms, a softmax,
+    a second GELU - has no expectation to be compared with, and the layer drops the mask half way through the graph: a
+    verdict of "OK" would claim a check that was not made.  Such a plan is refused, with the reason."""
+    from .plan import UnsupportedLayer
+    from .weights import attention_layers
+    names = attention_layers(plan) if plan is not None else []
+    if names:
+        raise UnsupportedLayer(f"verify-model does not cover cross_frame_attention layers ({', '.join(names)}): the graph census "
+                               "has no expectations for MultiHeadAttention / LayerNormalization nodes, and the SavedModel-bundle "
+                               "loader does not map their variables - load such a model from <name>.weights.npz "
+                               "(README: 'Attention models'; with a SavedModel directory beside it: --trust-project / "
+                               "JAEGER_TRUST_PROJECT=1)")
+
+
 def verify_model(graph_dir, plan: ModelPlan | None = None, legacy: bool = False) -> list[str]:
     """Findings (strings) where the SavedModel's census disagrees with the plan; [] = consistent."""
+    refuse_attention(plan)
     c = S.census(graph_dir)
     exp = _legacy_expectations() if legacy else _plan_expectations(plan)
     out: list[str] = []
@@ -99,6 +116,7 @@ def verify_model(graph_dir, plan: ModelPlan | None = None, legacy: bool = False)
 
 
 def report(graph_dir, plan: ModelPlan | None = None, legacy: bool = False) -> str:
+    refuse_attention(plan)
     c = S.census(graph_dir)
     findings = verify_model(graph_dir, plan, legacy)
     lines = [f"SavedModel {Path(graph_dir)}", f"  serving function {c['function']}: {c['n_nodes']} nodes, inputs "

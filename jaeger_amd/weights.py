@@ -16,7 +16,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .plan import Conv, Dense, ModelPlan, Nmd, Norm, ResBlock, weight_shapes
+from .plan import Conv, Dense, FrameAttn, ModelPlan, Nmd, Norm, ResBlock, weight_shapes
 
 
 def random_weights(plan: ModelPlan, seed: int = 38341) -> dict[str, np.ndarray]:
@@ -46,6 +46,27 @@ def save_npz(path, weights: dict[str, np.ndarray]) -> None:
 def load_npz(path) -> dict[str, np.ndarray]:
     z = np.load(path)
     return {k.replace(".", "/"): z[k] for k in z.files}
+
+
+def attention_layers(plan: ModelPlan) -> list[str]:
+    """Names of the plan's cross_frame_attention layers."""
+    return [l.name for seq in (plan.rep, plan.classifier, plan.reliability or []) for l in seq if isinstance(l, FrameAttn)]
+
+
+NPZ_ROUTE = ("export the model's variables under their canonical names (README: 'Attention models') into "
+             "<name>.weights.npz with numpy.savez - that route is supported")
+
+
+def _refuse_attention(plan: ModelPlan, what: str, source) -> None:
+    """The Keras-3 ``.weights.h5`` and SavedModel-bundle loaders map weight groups onto plan layers by order and shapes.
+    A MultiHeadAttention nests four EinsumDense sub-layers whose key scheme in either container could only be guessed
+    here (no checkpoint of such a model and no Keras to write one): a guessed scheme would be untestable, so both
+    loaders refuse such a plan and name the route that works."""
+    names = attention_layers(plan)
+    if names:
+        raise AttentionWeightsUnsupported(
+            f"{source}: the {what} loader does not map the nested MultiHeadAttention variables of "
+            f"cross_frame_attention layers ({', '.join(names)}); {NPZ_ROUTE}")
 
 
 def _layer_order(plan: ModelPlan) -> list[tuple[str, list[str]]]:
@@ -119,6 +140,7 @@ def load_keras3_h5(path, plan: ModelPlan) -> dict[str, np.ndarray]:
     layer takes the first unused group with its variable shapes in natural name order, which is
     creation order for same-type layers."""
     from .hdf5_lite import read_datasets
+    _refuse_attention(plan, "Keras-3 .weights.h5", path)
     shapes = weight_shapes(plan)
     by_group: dict[tuple[str, ...], dict[int, np.ndarray]] = {}
     for key, arr in read_datasets(path).items():
@@ -183,6 +205,11 @@ class BundleSchemeError(ValueError):
     with the weights file.  A bundle that IS understood and disagrees with the plan (a missing layer, a shape) stays fatal."""
 
 
+class AttentionWeightsUnsupported(BundleSchemeError):
+    """A plan with cross_frame_attention layers handed to the ``.weights.h5`` or the SavedModel-bundle loader (a stated
+    limit: :func:`_refuse_attention`).  As a :class:`BundleSchemeError` it lets `load_weights` go on to a ``.npz``."""
+
+
 _KNOWN_VARIABLES = {"kernel", "bias", "embeddings", "gamma", "beta", "moving_mean", "moving_variance", "alpha",
                     "layer_weights"}
 
@@ -245,6 +272,7 @@ def load_savedmodel_bundle(graph_dir, plan: ModelPlan) -> dict[str, np.ndarray]:
     by object-graph order and variable attribute names (:func:`assign_groups`), no shape heuristics."""
     from .savedmodel_lite import bundle_layer_groups
     vdir = Path(graph_dir) / "variables"
+    _refuse_attention(plan, "SavedModel variable-bundle", vdir)
     return assign_groups(bundle_layer_groups(vdir), _layer_order(plan), weight_shapes(plan), str(vdir))
 
 
