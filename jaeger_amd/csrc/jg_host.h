@@ -1,0 +1,86 @@
+// Host side of libjaeger_hip.so, shared by jg_engine / jg_model / jg_prepare / jg_run / jg_predict.hip: the two tables
+// every other piece reads - the shape record of each op at a row length, and where each op runs - and the few functions
+// that cross the files.  No kernel includes this header.
+#pragma once
+#include <string.h>
+
+#include <algorithm>
+
+#include "jg_common.h"
+#include "jg_small.h"
+#include "jg_resblock64.h"
+#include "jg_vecmax.h"
+#include "jg_frameattn.h"
+
+#pragma GCC visibility push(hidden)
+// ---- shapes: jg_shape_walk (jg_model.hip) is the only place that computes them -------------------------------------
+struct Shape {
+  int frames = 0, L = 0, C = 0;
+};
+struct OpShape {                // op i at l positions per row
+  Shape in, out;                // the tensor in in_buf (ids: (id_frames, l, cin)) and the one written (frames 0: none)
+  int L_out = 0, pad_left = 0;  // CONV / MASK geometry (MAXPOOL1D: L_out)
+  int m_in = 0, m_out = 0;      // MASK / EMBED: positions per frame of the mask read and written
+  int vec_need = 0;             // floats of out_vec this op needs (vec_off + its width)
+  Shape cvt[3];                 // the tensors converted in front of the op (ConvHPrep::cvt_slot), as they are then
+};
+int jg_shape_walk(const jg_model *m, int l, std::vector<OpShape> &shp);
+int jg_ensure_workspace(jg_model *m, int64_t chunk, int l, const std::vector<OpShape> &shp);
+
+// ---- placement: jg_place_op (jg_run.hip) is the only place that decides it -----------------------------------------
+enum Place {
+  PL_SMALL_SKIP,   // computed inside the small-window kernel: no launch
+  PL_SMALL_NMD,    // NMD_FINAL that finishes a tap the small-window kernel accumulated
+  PL_SMALL_POOL,   // POOL that finishes the small-window kernel's channel sums
+  PL_TAB_CONV,     // table net: conv + pool in this op's launch
+  PL_TAB_POOL,     // ... its pool: no launch
+  PL_RB_CONV1,     // conv1 of a fused residual block: computed by conv2's launch
+  PL_RB32,         // conv2 of a fused residual block: jg_resblock.hip
+  PL_RB64,         // ... jg_resblock64.hip
+  PL_CONV_F16,     // split-f16 conv
+  PL_CONV_F32,     // exact-f32 conv
+  PL_POOL_FUSED,   // POOL finished from the partials its split-f16 conv left
+  PL_ORDINARY,     // the op's own kernel
+};
+struct PlaceCtx {  // what placement depends on besides the model
+  int prec;        // 0 exact f32, 1 split-f16
+  bool fuse_rb;    // JG_OPT_FUSE_RESBLOCK
+  bool small, tab; // rows of this length fit the small-window kernel / the table net (false without a row length)
+};
+// of a run at l positions (shp = its shape walk); shp == nullptr: no row length, the layer-by-layer placement
+PlaceCtx jg_place_ctx(const jg_model *m, const std::vector<OpShape> *shp, int l);
+// the layer-by-layer placement in split-f16 mode under default options: what describe() and the statistics report
+static inline PlaceCtx jg_place_nominal() { return PlaceCtx{1, true, false, false}; }
+Place jg_place_op(const jg_model *m, size_t i, const PlaceCtx &c);
+static inline bool jg_place_is_f16(Place p) { return p == PL_RB_CONV1 || p == PL_RB32 || p == PL_RB64 || p == PL_CONV_F16; }
+
+// ---- the rest ----------------------------------------------------------------------------------------------------------
+int jg_prepare_tab(jg_model *m, const float *weights);          // jg_prepare.hip, in the order jg_model_create calls them
+int jg_prepare_f16(jg_model *m, const float *weights);
+int jg_plan_phase_split(jg_model *m, const float *weights);
+int jg_plan_resblocks(jg_model *m, const float *weights);
+int jg_prepare_f32(jg_model *m, const float *weights);
+int jg_prepare_small(jg_model *m, const float *weights);
+void jg_free_small(jg_model *m);
+const char *jg_tap_refusal(const jg_model *m, size_t i, const PlaceCtx &c, int l, char *why, size_t cap);   // jg_model.hip
+int jg_tap_copy(jg_model *m, size_t i, const OpShape &r, const PlaceCtx &c, int nw, hipStream_t s);
+int jg_effective_chunk(const jg_model *m, int chunk, int l, int64_t n_win);                                  // jg_run.hip
+int jg_forward_chunks(jg_model *m, const std::vector<OpShape> &shp, const uint8_t *d_ids, int64_t n_win, int l, float *prediction,
+                      float *reliability, float *embedding, float *nmd, int out_loc, int chunk, hipStream_t s);
+int jg_forward_device_ids(jg_model *m, const uint8_t *d_ids, int64_t n_win, int l, float *prediction, float *reliability,
+                          float *embedding, float *nmd, int out_loc, int chunk, hipStream_t s);
+
+static inline hipStream_t pick_stream(jg_engine *e, void *stream) {
+  return stream != nullptr ? reinterpret_cast<hipStream_t>(stream) : e->stream;
+}
+
+template <typename T>
+static int grow(T **p, int64_t *cap, int64_t need_bytes) {
+  if (need_bytes <= *cap) return JG_OK;
+  if (*p) JG_HIP(hipFree(*p));
+  *p = nullptr;
+  JG_HIP(hipMalloc(reinterpret_cast<void **>(p), (size_t)need_bytes));
+  *cap = need_bytes;
+  return JG_OK;
+}
+#pragma GCC visibility pop

@@ -58,7 +58,7 @@ def act(kind: int, x: np.ndarray) -> np.ndarray:
 
 
 def conv_geometry(l_in: int, k: int, stride: int, dil: int, padding: int) -> tuple[int, int]:
-    """(L_out, pad_left): TF SAME (pad_left = total // 2) or VALID - jg_api.hip conv_geometry."""
+    """(L_out, pad_left): TF SAME (pad_left = total // 2) or VALID - jg_model.hip conv_geometry."""
     if padding == PAD_SAME:
         lo = -(-l_in // stride)
         total = max((lo - 1) * stride + (k - 1) * dil + 1 - l_in, 0)

@@ -172,7 +172,7 @@ def compile_small(name: str, seed: int = 38341):
 
 
 class SmallNet:
-    """The fused kernel's view of a program, restated from the op stages (jg_api.hip prepare_small): per layer the first
+    """The fused kernel's view of a program, restated from the op stages (jg_prepare.hip jg_prepare_small): per layer the first
     affine folded in f64 (scale, shift), add / save / second affine / tap, the pool kind; ``codes()`` = the switch codes."""
 
     def __init__(self, prog):
