@@ -67,6 +67,16 @@ typedef enum {
                           with arg > 0, w1 [C][arg] | b1 [arg] | w2 [arg][C] | b2 [C]; out_mask = JG_BUF_NONE (the layer does not
                           set supports_masking: nothing behind it sees a mask); stages: bias / batch norm / unmasked DyT / activation.
                           C 32 or 64, key_dim 4 .. 64, arg <= 256: jg_model_create refuses other sizes with the reason */
+  JG_OP_LOCALATTN = 14, /* one block of LocalAttention (nnlib/v2/layers.py:2520-2645) as one launch: in_buf -> out_buf (NEVER the same
+                          slot: a tile reads its neighbours' positions), f32 rows (6, L, C) per window; banded self-attention along
+                          the length axis of every frame row: query q attends the keys k with |q - k| <= `stride` (the op's free
+                          integer field carries the half-window = window_size // 2; `dilation` stays 1) whose in_mask byte is set
+                          (in_mask = JG_BUF_NONE: every position of the row).  cin = cout = C, k = heads, arg = feed-forward width
+                          (always present), f0 = epsilon of the two layer norms, w_off = the packed weights in JG_OP_FRAMEATTN's
+                          layout.  out_mask = in_mask: the layer keeps the mask (supports_masking).  A query without a valid key
+                          in its band stores exact zeros.  stages: bias / batch norm / unmasked DyT / activation.  C 16, 32 or
+                          64, key_dim 4 .. 64, arg a multiple of 16 up to 256, half-window 0 .. 32: jg_model_create refuses
+                          other sizes with the reason */
   JG_OP_STRANDS = 10   /* a branched (shared-weight) model over the k strands of a nucleotide input: every strand is a
                           program row of its own (ids (W, k, L), one frame per row); arg = how the strands' predictions
                           merge (jg_merge_kind); the embedding output is their average.  builder.py:1195-1266, :776-791 */
@@ -312,8 +322,13 @@ int jg_profile_read(jg_engine *e, double *conv_ms, int64_t *conv_launches, doubl
  * the fused small-window network kernel, and the frame-attention kernel (FLOPs of its four dense products) */
 enum { JG_PROF_MFMA_F16X3 = 0, JG_PROF_MFMA_F32 = 1, JG_PROF_TABLE = 2, JG_PROF_FUSED_SMALL = 3, JG_PROF_FRAMEATTN = 4,
        JG_PROF_FRAMEATTN_CVT = 5 /* the F16S -> f32 layout conversion a split-f16 program queues in front of a frame-attention op */,
-       JG_PROF_CLASSES = 6 };
+       JG_PROF_LOCALATTN = 6 /* the local-attention kernel (FLOPs of its dense products, halo included) */,
+       JG_PROF_LOCALATTN_CVT = 7 /* the F16S -> f32 conversion queued in front of a local-attention op */,
+       JG_PROF_CLASSES = 8 };
 int jg_profile_read_class(jg_engine *e, int cls, double *ms, int64_t *launches, double *flops);
+/* query positions of one work item of the local-attention kernel (JG_OP_LOCALATTN): row lengths around it and its
+ * multiples are where a tile border, a halo and a ragged last tile meet */
+int jg_localattn_tile(void);
 
 /* Box calibration (bench.py's `box` object; no counterpart in the reference): about `seconds` (0 < seconds <= 30) of
  * back-to-back launches of a bare v_mfma_f32_32x32x16_f16 loop on random register operands, two waves per SIMD on every

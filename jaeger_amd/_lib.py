@@ -30,12 +30,14 @@ JG_COL_STRING, JG_COL_INT, JG_COL_FLOAT, JG_COL_BOOL, JG_COL_SPANS = 0, 1, 2, 3,
 JG_STAT_STREAM_GROUPS, JG_STAT_STREAM_BYTES, JG_STAT_PEAK_DEVICE_BASES, JG_STAT_DUST_MASKED, JG_STAT_WINDOWS_DONE = 1, 2, 3, 4, 5
 JG_MSTAT_CONVS, JG_MSTAT_CONVS_F16X3, JG_MSTAT_LAYOUT_CONVERSIONS, JG_MSTAT_SMALL_FUSED = 0, 1, 2, 3
 JG_MSTAT_TAP_VARIANT = 4
-JG_PROF_MFMA_F16X3, JG_PROF_MFMA_F32, JG_PROF_TABLE, JG_PROF_FUSED_SMALL, JG_PROF_FRAMEATTN, JG_PROF_FRAMEATTN_CVT = range(6)     # jg_profile_read_class
+JG_PROF_MFMA_F16X3, JG_PROF_MFMA_F32, JG_PROF_TABLE, JG_PROF_FUSED_SMALL, JG_PROF_FRAMEATTN, JG_PROF_FRAMEATTN_CVT, JG_PROF_LOCALATTN, JG_PROF_LOCALATTN_CVT = range(8)     # jg_profile_read_class
 # JG_MSTAT_TAP_VARIANT bits: the kernel variant the tapped op ran on (jg_model_set_tap)
 TAP_F16S, TAP_PHASE_SPLIT, TAP_WINDOW_PACKED, TAP_TABLE_LOOKUP, TAP_NARROW, TAP_EXACT_F32, TAP_FUSED_RESBLOCK = 1, 2, 4, 8, 16, 32, 64
 
 # jg_op_kind
-OP_CONV, OP_MASK, OP_POOL, OP_DENSE, OP_ELTWISE, OP_NMD_FINAL, OP_OODSIG, OP_MAXPOOL1D, OP_FRAMESUM, OP_STRANDS, OP_EMBED, OP_VECMAX, OP_FRAMEATTN = range(1, 14)
+OP_CONV, OP_MASK, OP_POOL, OP_DENSE, OP_ELTWISE, OP_NMD_FINAL, OP_OODSIG, OP_MAXPOOL1D, OP_FRAMESUM, OP_STRANDS, OP_EMBED, OP_VECMAX, OP_FRAMEATTN, OP_LOCALATTN = range(1, 15)
+LOCALATTN_TILE = 80          # jg_localattn_tile(): query positions of one work item of the local-attention kernel
+LOCALATTN_MAX_HALF = 32
 # jg_stage_kind
 ST_NONE, ST_BIAS, ST_BN, ST_DYT, ST_ADD, ST_ACT, ST_NMD, ST_MASKMUL, ST_LN = range(9)
 # jg_act
@@ -117,6 +119,7 @@ SYMBOLS = {
     "jg_profile_enable": (C.c_int, [_vp, C.c_int]),
     "jg_profile_read": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "jg_profile_read_class": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "jg_localattn_tile": (C.c_int, []),
     "jg_box_calibrate": (C.c_int, [_vp, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),
     "jg_terminal_repeats": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int32, _vp]),
     "jg_viterbi_decode": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int64, _vp, _vp]),

@@ -11,6 +11,7 @@
 #include "jg_resblock64.h"
 #include "jg_vecmax.h"
 #include "jg_frameattn.h"
+#include "jg_localattn.h"
 
 #pragma GCC visibility push(hidden)
 // ---- shapes: jg_shape_walk (jg_model.hip) is the only place that computes them -------------------------------------
@@ -40,6 +41,7 @@ enum Place {
   PL_CONV_F16,     // split-f16 conv
   PL_CONV_F32,     // exact-f32 conv
   PL_POOL_FUSED,   // POOL finished from the partials its split-f16 conv left
+  PL_LOCALATTN,    // local attention: jg_localattn.hip (f32 rows, out of place, the mask kept)
   PL_ORDINARY,     // the op's own kernel
 };
 struct PlaceCtx {  // what placement depends on besides the model

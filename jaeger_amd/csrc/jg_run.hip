@@ -42,6 +42,7 @@ Place jg_place_op(const jg_model *m, size_t i, const PlaceCtx &c) {
     if (c.fuse_rb && hp.rb_first >= 0) return op.cout == 64 ? PL_RB64 : PL_RB32;
     return PL_CONV_F16;
   }
+  if (op.kind == JG_OP_LOCALATTN) return PL_LOCALATTN;
   if (op.kind == JG_OP_POOL && c.prec == 1 && m->pool_fused_by[i] >= 0) return PL_POOL_FUSED;
   return PL_ORDINARY;
 }
@@ -141,9 +142,9 @@ static int convert_layouts(jg_model *m, size_t i, const OpShape &r, int nw, hipS
     const int64_t rows = (int64_t)nw * t.frames;
     // (the conversion in front of a frame-attention op is timed as a class of its own: what a kernel variant that
     // reads F16S directly would save)
-    const bool timed = e->profile && m->ops[i].kind == JG_OP_FRAMEATTN;
+    const bool timed = e->profile && (m->ops[i].kind == JG_OP_FRAMEATTN || m->ops[i].kind == JG_OP_LOCALATTN);
     ProfEvent pe;
-    int rc = timed ? prof_begin(e, s, JG_PROF_FRAMEATTN_CVT, 0.0, &pe) : JG_OK;
+    int rc = timed ? prof_begin(e, s, m->ops[i].kind == JG_OP_LOCALATTN ? JG_PROF_LOCALATTN_CVT : JG_PROF_FRAMEATTN_CVT, 0.0, &pe) : JG_OK;
     if (rc != JG_OK) return rc;
     if (hq.cvt_to_f32[q]) rc = jg_launch_f16s_to_f32(reinterpret_cast<const uint4 *>(m->act[slot]), rows, t.L, t.C, m->cvt_scratch, s);
     else rc = jg_launch_f32_to_f16s(m->act[slot], rows, t.L, t.C, reinterpret_cast<uint4 *>(m->cvt_scratch), s, m->d_overflow);
@@ -418,6 +419,29 @@ static int launch_frameattn(jg_model *m, size_t i, const OpShape &r, int nw, hip
   return prof_end(e, s, &pe, jg_launch_frameattn(e, a, s));
 }
 
+// one block of local attention: out of place, key validity from the op's mask slot (which it leaves as it is)
+static int launch_localattn(jg_model *m, size_t i, const OpShape &r, int nw, hipStream_t s) {
+  jg_engine *e = m->e;
+  const jg_op &op = m->ops[i];
+  JgLocalAttnArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = m->act[op.in_buf];
+  a.y = m->act[op.out_buf];
+  a.mask = op.in_mask >= 0 ? m->msk[op.in_mask] : nullptr;
+  a.w = m->d_w + op.w_off;
+  a.rows = nw * r.in.frames; a.L = r.in.L; a.tiles = (r.in.L + JG_LOCALATTN_TILE - 1) / JG_LOCALATTN_TILE;
+  a.C = op.cin; a.H = op.k; a.D = op.cin / op.k; a.F = op.arg;
+  a.half = op.stride;
+  a.eps = op.f0;
+  resolve_stages(m, op, a.st, &a.n_stages);
+  const int hb = (a.half + 15) / 16;
+  const double kv_share = (double)(JG_LOCALATTN_TILE + 32 * hb) / JG_LOCALATTN_TILE;
+  ProfEvent pe;
+  int rc = prof_begin(e, s, JG_PROF_LOCALATTN, 2.0 * ((2.0 + 2.0 * kv_share) * a.C * a.C + 2.0 * a.C * a.F) * (double)a.rows * r.in.L, &pe);
+  if (rc != JG_OK) return rc;
+  return prof_end(e, s, &pe, jg_launch_localattn(e, a, s));
+}
+
 static int launch_nmd_final(jg_model *m, size_t i, const OpShape &r, int nw, hipStream_t s) {
   // op.arg = partial slot, in_mask = mask the tap used, cout = channels,
   // in_buf = activation slot whose shape gives the position count
@@ -505,6 +529,7 @@ static int run_chunk(jg_model *m, const std::vector<OpShape> &shp, const uint8_t
       case PL_POOL_FUSED:
         rc = jg_launch_pool_final(m->pool_part, m->pool_rows, nw, r.in.C, m->vec[op.out_vec] + op.vec_off, m->vec_w[op.out_vec], s);
         break;
+      case PL_LOCALATTN: rc = launch_localattn(m, i, r, nw, s); break;
       case PL_ORDINARY: rc = launch_ordinary(m, i, r, d_ids, nw, s); break;
     }
     if (rc != JG_OK) return rc;

@@ -198,6 +198,17 @@ class HipDevice:
             out[name] = {"ms": ms.value, "launches": n.value, "flops": fl.value}
         return out
 
+    def profile_read_local_attn(self) -> dict:
+        """The profiling classes of the local-attention op (``profile_read`` keeps the keys it had before the op existed):
+        ``local_attn`` - its launches, with the FLOPs of the dense products, halo included; ``local_attn_cvt`` - the
+        F16S -> f32 conversions a split-f16 program queues in front of them."""
+        ms, n, fl = C.c_double(), C.c_int64(), C.c_double()
+        out = {}
+        for cls, name in ((L.JG_PROF_LOCALATTN, "local_attn"), (L.JG_PROF_LOCALATTN_CVT, "local_attn_cvt")):
+            L.check(self.lib.jg_profile_read_class(self.handle, cls, C.byref(ms), C.byref(n), C.byref(fl)))
+            out[name] = {"ms": ms.value, "launches": n.value, "flops": fl.value}
+        return out
+
     def box_calibrate(self, seconds: float = 0.5) -> dict:
         """``jg_box_calibrate``: a bare ``v_mfma_f32_32x32x16_f16`` loop on random register operands for about ``seconds``
         of back-to-back launches - the dense f16 matrix-core rate and the in-kernel shader clock THIS device holds under

@@ -125,6 +125,45 @@ def frame_attn_limit(channels: int, heads: int, ff_dim: int) -> str | None:
 
 
 @dataclass
+class LocalAttn:
+    """One LocalAttention layer (layers.py:2520-2645): windowed self-attention along the length axis inside every frame
+    row, ``blocks`` times: pre-LN (eps 1e-6, :2556-2558) -> MultiHeadAttention(num_heads, key_dim = channels //
+    num_heads, :2559-2564) under the mask ``|q - k| <= half_window and mask[k]`` (:2579-2585, :2604-2609) -> residual
+    (:2619); LN -> Dense(ff_dim, gelu) -> Dense(channels) -> residual (:2621-2623), always present.  The layer sets
+    supports_masking and ``compute_mask`` returns the mask (:2550, :2627-2628): the mask stays behind it."""
+    name: str
+    channels: int
+    heads: int
+    key_dim: int
+    ff_dim: int
+    half_window: int               # window_size // 2 (:2581)
+    blocks: int = 1                # num_blocks (:2538)
+
+
+#: what the local-attention kernel (csrc/jg_localattn.hip) covers
+LOCALATTN_CHANNELS = (16, 32, 64)
+LOCALATTN_KEY_DIMS = (4, 8, 16, 32, 64)
+LOCALATTN_MAX_FF = 256
+LOCALATTN_MAX_HALF = 32
+_LOCALATTN_REQUIRED = ("embed_dim", "num_heads", "feed_forward_dim", "window_size")   # no defaults (layers.py:2531-2537)
+
+
+def local_attn_limit(channels: int, heads: int, ff_dim: int, half_window: int) -> str | None:
+    """Why the local-attention kernel cannot run this size, or None."""
+    if channels not in LOCALATTN_CHANNELS:
+        return f"embed_dim {channels} (the kernel covers {' / '.join(map(str, LOCALATTN_CHANNELS))} channels)"
+    if heads < 1 or channels % heads or channels // heads not in LOCALATTN_KEY_DIMS:
+        return (f"num_heads {heads} at embed_dim {channels} (key_dim = embed_dim / num_heads must be one of "
+                f"{', '.join(map(str, LOCALATTN_KEY_DIMS))})")
+    if ff_dim % 16 or not 16 <= ff_dim <= LOCALATTN_MAX_FF:
+        return f"feed_forward_dim {ff_dim} (a multiple of 16 up to {LOCALATTN_MAX_FF})"
+    if not 0 <= half_window <= LOCALATTN_MAX_HALF:
+        return (f"window_size {2 * half_window} or more (the kernel covers half-windows of 0 to {LOCALATTN_MAX_HALF} "
+                f"positions, window_size up to {2 * LOCALATTN_MAX_HALF + 1})")
+    return None
+
+
+@dataclass
 class ModelPlan:
     vocab: int
     embedding_dim: int
@@ -284,6 +323,26 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
             if why is not None:
                 raise UnsupportedLayer(f"{p}: cross_frame_attention with {why}")
             out.append(FrameAttn(p, c, h, c // h, f, use_ffn))
+        elif name == "local_attention" and all(k in cfg for k in _LOCALATTN_REQUIRED):
+            # builder.py:290, :1155: LocalAttention(**config) (embed_dim, num_heads, feed_forward_dim, window_size,
+            # dropout_rate, num_blocks); an entry without one of the four required arguments raises in the reference's
+            # constructor and falls through to the generic refusal below
+            if frames is None:
+                raise UnsupportedLayer(f"{p}: local_attention needs the (frames, length, channels) tensor of the "
+                                       "representation learner: not supported in a head or on a strand branch")
+            c, h, f = int(cfg["embed_dim"]), int(cfg["num_heads"]), int(cfg["feed_forward_dim"])
+            window, blocks = int(cfg["window_size"]), int(cfg.get("num_blocks", 1))
+            if window < 1:
+                raise UnsupportedLayer(f"{p}: local_attention window_size {window} (must be positive, layers.py:2542-2543)")
+            if blocks < 1:
+                raise UnsupportedLayer(f"{p}: local_attention num_blocks {blocks} (at least one block)")
+            if c != cin:
+                raise UnsupportedLayer(f"{p}: embed_dim {c} != {cin} incoming channels (the layer's residual adds them, "
+                                       "layers.py:2619)")
+            why = local_attn_limit(c, h, f, window // 2)
+            if why is not None:
+                raise UnsupportedLayer(f"{p}: local_attention with {why}")
+            out.append(LocalAttn(p, c, h, c // h, f, window // 2, blocks))
         else:
             raise UnsupportedLayer(
                 f"{p}: layer {name!r} is outside the Conv1D -> norm -> pool -> dense family "
@@ -521,6 +580,8 @@ def weight_shapes(plan: ModelPlan) -> dict[str, tuple]:
                     out[f"{layer.name}/bias"] = (layer.units,)
             elif isinstance(layer, FrameAttn):
                 out.update(frame_attn_weight_shapes(layer))
+            elif isinstance(layer, LocalAttn):
+                out.update(local_attn_weight_shapes(layer))
         if seq is plan.rep and plan.nmd_merge_mode != "concat":                 # NMDMerge is built behind the rep block's layers
             for i, d in enumerate(plan.nmd_dims):
                 out[f"rep/nmd_merge/proj_{i}/kernel"] = (d, plan.nmd_merge_dim)
@@ -544,6 +605,25 @@ def frame_attn_weight_shapes(a: FrameAttn) -> dict[str, tuple]:
         out.update({f"{a.name}/ffn_norm/gamma": (c,), f"{a.name}/ffn_norm/beta": (c,),
                     f"{a.name}/ffn_dense1/kernel": (c, f), f"{a.name}/ffn_dense1/bias": (f,),
                     f"{a.name}/ffn_dense2/kernel": (f, c), f"{a.name}/ffn_dense2/bias": (c,)})
+    return out
+
+
+def local_attn_weight_shapes(a: LocalAttn) -> dict[str, tuple]:
+    """Keras variable shapes of one LocalAttention layer, per block ``<name>/block<j>/``: the two LayerNormalization
+    layers' gamma / beta (C); MultiHeadAttention query / key / value EinsumDense kernels (C, H, D) with biases (H, D),
+    attention_output kernel (H, D, C) with bias (C); the two Dense layers of the feed-forward half."""
+    c, h, d, f = a.channels, a.heads, a.key_dim, a.ff_dim
+    out: dict[str, tuple] = {}
+    for j in range(a.blocks):
+        b = f"{a.name}/block{j}"
+        out.update({f"{b}/ln1/gamma": (c,), f"{b}/ln1/beta": (c,)})
+        for part in ("query", "key", "value"):
+            out[f"{b}/mha/{part}/kernel"] = (c, h, d)
+            out[f"{b}/mha/{part}/bias"] = (h, d)
+        out[f"{b}/mha/attention_output/kernel"] = (h, d, c)
+        out[f"{b}/mha/attention_output/bias"] = (c,)
+        out.update({f"{b}/ln2/gamma": (c,), f"{b}/ln2/beta": (c,), f"{b}/ffn1/kernel": (c, f), f"{b}/ffn1/bias": (f,),
+                    f"{b}/ffn2/kernel": (f, c), f"{b}/ffn2/bias": (c,)})
     return out
 
 

@@ -11,6 +11,8 @@ conv launches with epilogue stages:
 * each conv with masking gets one tiny mask op (``layers.py:1226-1255``).
 * ``cross_frame_attention -> norm -> activation``             one frame-attention op (``layers.py:2283-2384``); no mask
   leaves it
+* ``local_attention -> norm -> activation``                   one local-attention op per block (``layers.py:2520-2645``),
+  out of place, the mask kept; the norm / activation ride the last block's store
 
 Pure host logic (numpy + ctypes structs): unit-tested on CPU.
 """
@@ -22,7 +24,7 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 from . import _lib as L
-from .plan import Act, Conv, Dense, FrameAttn, ModelPlan, Nmd, Norm, ResBlock, UnsupportedLayer, weight_shapes
+from .plan import Act, Conv, Dense, FrameAttn, LocalAttn, ModelPlan, Nmd, Norm, ResBlock, UnsupportedLayer, weight_shapes
 
 _ACT_CODE = {None: L.ACT_NONE, "linear": L.ACT_NONE, "gelu": L.ACT_GELU_TANH, "gelu_erf": L.ACT_GELU_ERF,
              "relu": L.ACT_RELU, "tanh": L.ACT_TANH, "sigmoid": L.ACT_SIGMOID}
@@ -113,6 +115,23 @@ def pack_frame_attn(a: FrameAttn, w: dict[str, np.ndarray]) -> np.ndarray:
     return np.concatenate([x.ravel() for x in out]).astype(np.float32)
 
 
+LOCAL_ATTN_EPSILON = 1e-6      # both LayerNormalization layers of a LocalAttention block (layers.py:2556-2558, :2565-2567)
+
+
+def pack_local_attn(a: LocalAttn, block: int, w: dict[str, np.ndarray]) -> np.ndarray:
+    """The weights of block ``block`` of a LocalAttention layer as the kernel reads them (csrc/jg_localattn.hip):
+    :func:`pack_frame_attn`'s fold and layout - ln1 / ln2 gamma and beta into the q / k / v kernels and into ffn1, the
+    query's ``1 / sqrt(key_dim)`` into its kernel and bias, in float64."""
+    p = f"{a.name}/block{block}"
+    leaf = {"ln1": "attn_norm", "ln2": "ffn_norm", "ffn1": "ffn_dense1", "ffn2": "ffn_dense2", "mha": "mha"}
+    renamed = {}
+    for name, v in w.items():
+        if name.startswith(p + "/"):
+            head, rest = name[len(p) + 1:].split("/", 1)
+            renamed[f"{p}/{leaf[head]}/{rest}"] = v
+    return pack_frame_attn(FrameAttn(p, a.channels, a.heads, a.key_dim, a.ff_dim, True), renamed)
+
+
 @dataclass
 class Program:
     ops: list            # list[L.JgOp]
@@ -138,7 +157,8 @@ class Program:
             st = "+".join(stk[op.stages[s].kind] for s in range(op.n_stages))
             rows.append(f"{kinds[op.kind][3:]:9s} in={op.in_buf} out={op.out_buf} m={op.in_mask}->{op.out_mask} "
                         f"k={op.k} c={op.cin}->{op.cout} s={op.stride} d={op.dilation} [{st}]"
-                        + (f" heads={op.k} ff={op.arg}" if op.kind == L.OP_FRAMEATTN else ""))
+                        + (f" heads={op.k} ff={op.arg}" if op.kind == L.OP_FRAMEATTN else "")
+                        + (f" heads={op.k} ff={op.arg} half_window={op.stride}" if op.kind == L.OP_LOCALATTN else ""))
         return rows
 
 
@@ -160,6 +180,12 @@ class _Compiler:
         # the taps write the model's nmd output itself - or, under an NMDMerge that projects (sum / mean / max / weighted),
         # a scratch vector the merge reads (the two last vector slots: the heads use the ones from VEC_SCRATCH0 up)
         self.nmd_vec = L.VEC_NMD if plan.nmd_merge_mode == "concat" else L.JG_MAX_VECS - 1
+        # dead positions behind a masked local_attention (queries without a valid key in their band: the op writes zeros
+        # where Keras' value depends on its version and precision).  They are masked, and stay harmless as long as every
+        # later reader masks: None = the tensor holds none; else how many positions a later output mask may still grow
+        # before it would validate one (a dead position lies more than half_window away from every valid one)
+        self.dead_margin: int | None = None
+        self.dead_layer = ""
 
     # ---- helpers -----------------------------------------------------------
     def _op(self, kind, **kw):
@@ -265,6 +291,8 @@ class _Compiler:
             elif isinstance(nxt, Norm) and nxt.kind in ("masked_batchnorm", "masked_dyt", "masked_layernorm"):
                 stages.append(self._norm_stage(nxt, mask != L.JG_BUF_NONE))
                 if nxt.kind == "masked_batchnorm" and not nxt.use_masking:
+                    self._refuse_unmasked_reader(f"{nxt.name}: masked_batchnorm with use_masking: false (it drops the mask "
+                                                 "for every layer behind it)")
                     mask = L.JG_BUF_NONE          # supports_masking False drops the mask (layers.py:816)
             elif isinstance(nxt, Act):
                 stages.append(self._stage(L.ST_ACT, arg=act_code(nxt.kind)))
@@ -272,6 +300,12 @@ class _Compiler:
                 break
             i += 1
         return i, mask
+
+    def _refuse_unmasked_reader(self, what: str) -> None:
+        if self.dead_margin is not None:
+            raise UnsupportedLayer(f"{what} behind {self.dead_layer}: it reads masked positions unmasked, and local_attention "
+                                   "leaves zeros at positions whose band holds no valid key, where the Keras graph holds "
+                                   "values that depend on its version and precision")
 
     def _flush_nmd(self, pending: list, buf: int):
         for nmd, slot, mask in pending:
@@ -308,6 +342,9 @@ class _Compiler:
                 pos = dict(w_off=self.blob.add(pe), k=POSITION_ROWS)
             self.ops.append(self._op(L.OP_EMBED, out_buf=buf, out_mask=mask, cout=plan.embedding_dim, b_off=self.emb_off, **pos))
         i = 0
+        if layers and isinstance(layers[0], LocalAttn):
+            raise UnsupportedLayer(f"{layers[0].name}: local_attention directly on the embedding is not supported (the reference's "
+                                   "stacks put a conv in front of it; the embedding's rows at invalid codons are not zeros)")
         if not layers or not isinstance(layers[0], Conv):
             # A norm / activation / nmd / residual block - or the pool itself - directly on the Embedding output (the
             # reference's own Embedding -> MaskedBatchNorm -> masked max pool case, tests/unit/test_masked_pooling.py:
@@ -329,6 +366,9 @@ class _Compiler:
             layer = layers[i]
             pending: list = []
             if isinstance(layer, Conv):
+                if not layer.use_masking or mask == L.JG_BUF_NONE:
+                    self._refuse_unmasked_reader(f"{layer.name}: a conv without masking")
+                self.dead_margin = None           # a masked conv reads valid positions only: its output holds no dead value
                 om = self._conv_mask(layer, mask)
                 stages = self._base_stages(layer)
                 i, om2 = self._fuse_tail(layers, i + 1, stages, om, layer.filters, pending)
@@ -341,6 +381,18 @@ class _Compiler:
                 buf, mask = out, om2
             elif isinstance(layer, ResBlock):
                 blk = layer
+                if not blk.use_masking or mask == L.JG_BUF_NONE:
+                    self._refuse_unmasked_reader(f"{blk.name}: a residual block without masking")
+                if self.dead_margin is not None and blk.conv3 is None:
+                    # the shortcut adds the block's input as it is (layers.py:1907-1913) while the two convs grow the mask
+                    span = (blk.conv1.kernel_size - 1) * blk.conv1.dilation_rate
+                    grow = 2 * (span - span // 2)
+                    if grow > self.dead_margin:
+                        self._refuse_unmasked_reader(f"{blk.name}: a residual block whose output mask grows by {grow} positions "
+                                                     f"(its shortcut carries the input's masked positions; room {self.dead_margin})")
+                    self.dead_margin -= grow
+                elif blk.conv3 is not None:
+                    self.dead_margin = None       # every path into the output is a masked conv
                 in_mask = mask if blk.use_masking else L.JG_BUF_NONE
                 m1 = self._conv_mask(blk.conv1, in_mask)
                 b1 = self.bufs.take()
@@ -398,6 +450,7 @@ class _Compiler:
             elif isinstance(layer, FrameAttn):
                 if buf == L.JG_BUF_IDS:
                     raise UnsupportedLayer(f"{layer.name}: cross_frame_attention directly on the embedding is not supported")
+                self._refuse_unmasked_reader(f"{layer.name}: cross_frame_attention (it attends over all six frames of a position)")
                 # CrossFrameAttention does not set supports_masking (layers.py:2283-2384): the norm / activation / pool / conv
                 # behind it see NO mask, and the values the network holds at masked positions flow on as they are.  The
                 # norm / activation that follow fuse into the op's store; a LayerNorm is cut off into its own op
@@ -423,6 +476,40 @@ class _Compiler:
                 self.bufs.give(buf)
                 self.masks.give(mask)
                 buf, mask = out, L.JG_BUF_NONE
+            elif isinstance(layer, LocalAttn):
+                if buf == L.JG_BUF_IDS:
+                    raise UnsupportedLayer(f"{layer.name}: local_attention directly on the embedding is not supported")
+                # LocalAttention keeps the mask (supports_masking, compute_mask returns it: layers.py:2550, :2627-2628): the
+                # bias / batch norm / unmasked DyT / activation that follow ride the LAST block's store; a LayerNorm or a
+                # masked DyT is cut off into an element-wise op behind it
+                if mask != L.JG_BUF_NONE:
+                    self.dead_margin = layer.half_window if self.dead_margin is None else min(self.dead_margin, layer.half_window)
+                    self.dead_layer = f"{layer.name} (local_attention)"
+                stages = []
+                i, mask2 = self._fuse_tail(layers, i + 1, stages, mask, layer.channels, pending)
+                if pending:
+                    raise UnsupportedLayer(f"{layer.name}: an nmd tap directly behind local_attention is not supported "
+                                           "(the op's store carries no partial sums)")
+                tail = []
+                for j, st in enumerate(stages):
+                    if st.kind == L.ST_LN or (st.kind == L.ST_DYT and st.arg == 1):
+                        stages, tail = stages[:j], stages[j:]
+                        break
+                # one op per block, never in place (a tile reads its neighbours' positions as its halo): two slots ping-pong
+                for j in range(layer.blocks):
+                    out = self.bufs.take()
+                    op = self._op(L.OP_LOCALATTN, in_buf=buf, out_buf=out, in_mask=mask, out_mask=mask, k=layer.heads,
+                                  cin=layer.channels, cout=layer.channels, arg=layer.ff_dim, stride=layer.half_window,
+                                  f0=LOCAL_ATTN_EPSILON, w_off=self.blob.add(pack_local_attn(layer, j, self.w)))
+                    if j == layer.blocks - 1:
+                        op.n_stages = len(stages)
+                        for q, st in enumerate(stages):
+                            op.stages[q] = st
+                    self.ops.append(op)
+                    self.bufs.give(buf)
+                    buf = out
+                self._emit_ln_tail(layer.name, tail, mask, buf, layer.channels)
+                mask = mask2
             elif isinstance(layer, Nmd):
                 raise UnsupportedLayer("an nmd layer must directly follow a conv or residual block")
             else:

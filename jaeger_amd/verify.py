@@ -54,10 +54,10 @@ def refuse_attention(plan: ModelPlan | None) -> None:
     a second GELU - has no expectation to be compared with, and the layer drops the mask half way through the graph: a
     verdict of "OK" would claim a check that was not made.  Such a plan is refused, with the reason."""
     from .plan import UnsupportedLayer
-    from .weights import attention_layers
+    from .weights import attention_kinds, attention_layers
     names = attention_layers(plan) if plan is not None else []
     if names:
-        raise UnsupportedLayer(f"verify-model does not cover cross_frame_attention layers ({', '.join(names)}): the graph census "
+        raise UnsupportedLayer(f"verify-model does not cover {attention_kinds(plan)} layers ({', '.join(names)}): the graph census "
                                "has no expectations for MultiHeadAttention / LayerNormalization nodes, and the SavedModel-bundle "
                                "loader does not map their variables - load such a model from <name>.weights.npz "
                                "(README: 'Attention models'; with a SavedModel directory beside it: --trust-project / "

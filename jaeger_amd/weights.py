@@ -16,7 +16,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .plan import Conv, Dense, FrameAttn, ModelPlan, Nmd, Norm, ResBlock, weight_shapes
+from .plan import Conv, Dense, FrameAttn, LocalAttn, ModelPlan, Nmd, Norm, ResBlock, weight_shapes
 
 
 def random_weights(plan: ModelPlan, seed: int = 38341) -> dict[str, np.ndarray]:
@@ -49,8 +49,17 @@ def load_npz(path) -> dict[str, np.ndarray]:
 
 
 def attention_layers(plan: ModelPlan) -> list[str]:
-    """Names of the plan's cross_frame_attention layers."""
-    return [l.name for seq in (plan.rep, plan.classifier, plan.reliability or []) for l in seq if isinstance(l, FrameAttn)]
+    """Names of the plan's cross_frame_attention and local_attention layers."""
+    return [l.name for seq in (plan.rep, plan.classifier, plan.reliability or []) for l in seq
+            if isinstance(l, (FrameAttn, LocalAttn))]
+
+
+def attention_kinds(plan: ModelPlan) -> str:
+    """The YAML names of the attention layer kinds the plan holds, for the refusals that name them."""
+    layers = [l for seq in (plan.rep, plan.classifier, plan.reliability or []) for l in seq]
+    kinds = [name for cls, name in ((FrameAttn, "cross_frame_attention"), (LocalAttn, "local_attention"))
+             if any(isinstance(l, cls) for l in layers)]
+    return " / ".join(kinds)
 
 
 NPZ_ROUTE = ("export the model's variables under their canonical names (README: 'Attention models') into "
@@ -66,7 +75,7 @@ def _refuse_attention(plan: ModelPlan, what: str, source) -> None:
     if names:
         raise AttentionWeightsUnsupported(
             f"{source}: the {what} loader does not map the nested MultiHeadAttention variables of "
-            f"cross_frame_attention layers ({', '.join(names)}); {NPZ_ROUTE}")
+            f"{attention_kinds(plan)} layers ({', '.join(names)}); {NPZ_ROUTE}")
 
 
 def _layer_order(plan: ModelPlan) -> list[tuple[str, list[str]]]:
