@@ -77,6 +77,17 @@ typedef enum {
                           in its band stores exact zeros.  stages: bias / batch norm / unmasked DyT / activation.  C 16, 32 or
                           64, key_dim 4 .. 64, arg a multiple of 16 up to 256, half-window 0 .. 32: jg_model_create refuses
                           other sizes with the reason */
+  JG_OP_LENGTHATTN = 15, /* one TransformerEncoder along the length axis (nnlib/v2/layers.py:2206-2280; the length half of
+                          AxialAttention, :2400-2517) as one launch: in_buf -> out_buf (NEVER the same slot: every query tile
+                          reads the whole row), f32 rows (6, L, C) per window; full self-attention over the L positions of every
+                          frame row under M[q, k] = mask[q] and mask[k] (in_mask = JG_BUF_NONE: every position is a valid query
+                          and key): a valid query takes its softmax over the valid keys, a masked query's context is exactly
+                          zero (its attention output is the projection's bias) and the feed-forward half runs on it all the
+                          same.  cin = cout = C, k = heads, arg = feed-forward width (always present), f0 = epsilon of the two
+                          layer norms (1e-6), w_off = the packed weights in JG_OP_FRAMEATTN's layout.  out_mask = in_mask
+                          (inside an axial layer, which keeps the mask) or JG_BUF_NONE (a stand-alone encoder drops it).
+                          stages: bias / batch norm / unmasked DyT / activation.  C 16, 32 or 64, key_dim 4 .. 64, arg a
+                          multiple of 16 up to 256: jg_model_create refuses other sizes with the reason */
   JG_OP_STRANDS = 10   /* a branched (shared-weight) model over the k strands of a nucleotide input: every strand is a
                           program row of its own (ids (W, k, L), one frame per row); arg = how the strands' predictions
                           merge (jg_merge_kind); the embedding output is their average.  builder.py:1195-1266, :776-791 */
@@ -329,6 +340,10 @@ int jg_profile_read_class(jg_engine *e, int cls, double *ms, int64_t *launches, 
 /* query positions of one work item of the local-attention kernel (JG_OP_LOCALATTN): row lengths around it and its
  * multiples are where a tile border, a halo and a ragged last tile meet */
 int jg_localattn_tile(void);
+/* the length-attention kernel (JG_OP_LENGTHATTN): query positions of one workgroup, and key positions that go through
+ * LDS at a time - row lengths around them are where a ragged last tile and a ragged last chunk lie */
+int jg_lengthattn_tile(void);
+int jg_lengthattn_chunk(void);
 
 /* Box calibration (bench.py's `box` object; no counterpart in the reference): about `seconds` (0 < seconds <= 30) of
  * back-to-back launches of a bare v_mfma_f32_32x32x16_f16 loop on random register operands, two waves per SIMD on every

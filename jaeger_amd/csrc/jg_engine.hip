@@ -17,6 +17,8 @@ void jg_set_error(const char *fmt, ...) {
 extern "C" const char *jg_last_error(void) { return g_err; }
 extern "C" int jg_abi_version(void) { return JG_ABI_VERSION; }
 extern "C" int jg_localattn_tile(void) { return JG_LOCALATTN_TILE; }
+extern "C" int jg_lengthattn_tile(void) { return JG_LENGTHATTN_TILE; }
+extern "C" int jg_lengthattn_chunk(void) { return JG_LENGTHATTN_CHUNK; }
 extern "C" int jg_sizeof(int which) {
   return which == 0 ? (int)sizeof(jg_op) : (which == 1 ? (int)sizeof(jg_stage) : -1);
 }

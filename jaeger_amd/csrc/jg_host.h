@@ -12,6 +12,7 @@
 #include "jg_vecmax.h"
 #include "jg_frameattn.h"
 #include "jg_localattn.h"
+#include "jg_lengthattn.h"
 
 #pragma GCC visibility push(hidden)
 // ---- shapes: jg_shape_walk (jg_model.hip) is the only place that computes them -------------------------------------
@@ -43,6 +44,7 @@ enum Place {
   PL_POOL_FUSED,   // POOL finished from the partials its split-f16 conv left
   PL_LOCALATTN,    // local attention: jg_localattn.hip (f32 rows, out of place, the mask kept)
   PL_ORDINARY,     // the op's own kernel
+  PL_LENGTHATTN,   // full-row length attention: jg_lengthattn.hip (f32 rows, out of place)
 };
 struct PlaceCtx {  // what placement depends on besides the model
   int prec;        // 0 exact f32, 1 split-f16

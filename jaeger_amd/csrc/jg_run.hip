@@ -43,6 +43,7 @@ Place jg_place_op(const jg_model *m, size_t i, const PlaceCtx &c) {
     return PL_CONV_F16;
   }
   if (op.kind == JG_OP_LOCALATTN) return PL_LOCALATTN;
+  if (op.kind == JG_OP_LENGTHATTN) return PL_LENGTHATTN;
   if (op.kind == JG_OP_POOL && c.prec == 1 && m->pool_fused_by[i] >= 0) return PL_POOL_FUSED;
   return PL_ORDINARY;
 }
@@ -442,6 +443,23 @@ static int launch_localattn(jg_model *m, size_t i, const OpShape &r, int nw, hip
   return prof_end(e, s, &pe, jg_launch_localattn(e, a, s));
 }
 
+// one TransformerEncoder along the length: out of place, query / key validity from the op's mask slot (left as it is).
+// The op has no profiling class of its own (scripts/lengthattn_perf.py times it with events around whole programs)
+static int launch_lengthattn(jg_model *m, size_t i, const OpShape &r, int nw, hipStream_t s) {
+  const jg_op &op = m->ops[i];
+  JgLengthAttnArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = m->act[op.in_buf];
+  a.y = m->act[op.out_buf];
+  a.mask = op.in_mask >= 0 ? m->msk[op.in_mask] : nullptr;
+  a.w = m->d_w + op.w_off;
+  a.rows = nw * r.in.frames; a.L = r.in.L; a.tiles = (r.in.L + JG_LENGTHATTN_TILE - 1) / JG_LENGTHATTN_TILE;
+  a.C = op.cin; a.H = op.k; a.D = op.cin / op.k; a.F = op.arg;
+  a.eps = op.f0;
+  resolve_stages(m, op, a.st, &a.n_stages);
+  return jg_launch_lengthattn(m->e, a, s);
+}
+
 static int launch_nmd_final(jg_model *m, size_t i, const OpShape &r, int nw, hipStream_t s) {
   // op.arg = partial slot, in_mask = mask the tap used, cout = channels,
   // in_buf = activation slot whose shape gives the position count
@@ -530,6 +548,7 @@ static int run_chunk(jg_model *m, const std::vector<OpShape> &shp, const uint8_t
         rc = jg_launch_pool_final(m->pool_part, m->pool_rows, nw, r.in.C, m->vec[op.out_vec] + op.vec_off, m->vec_w[op.out_vec], s);
         break;
       case PL_LOCALATTN: rc = launch_localattn(m, i, r, nw, s); break;
+      case PL_LENGTHATTN: rc = launch_lengthattn(m, i, r, nw, s); break;
       case PL_ORDINARY: rc = launch_ordinary(m, i, r, d_ids, nw, s); break;
     }
     if (rc != JG_OK) return rc;

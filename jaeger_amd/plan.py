@@ -164,6 +164,78 @@ def local_attn_limit(channels: int, heads: int, ff_dim: int, half_window: int) -
 
 
 @dataclass
+class LengthAttn:
+    """One stand-alone TransformerEncoder layer (layers.py:2206-2280) with ``attention_axes = 2``: full self-attention
+    along the length axis inside every frame row - pre-LN (eps 1e-6, :2224-2226) -> MultiHeadAttention(num_heads, key_dim
+    = channels // num_heads, :2227-2233) under Keras 3's implicit query / value masks -> residual (:2256); LN ->
+    Dense(ff_dim, gelu) -> Dense(channels) -> residual (:2259-2264).  The layer does not set supports_masking: no mask
+    leaves it."""
+    name: str
+    channels: int
+    heads: int
+    key_dim: int
+    ff_dim: int
+
+
+@dataclass
+class AxialAttn:
+    """One AxialAttention layer (layers.py:2400-2517): per block a TransformerEncoder along the length (:2461-2470), a
+    CrossFrameAttention with its feed-forward half (:2474-2483), the post norm and the residual add of the block's input
+    (:2485-2501).  Only block 0's encoder sees the layer's incoming mask; ``masked_layernorm`` / ``masked_dyt`` post norms
+    get it in every block (:2495-2496).  The layer sets supports_masking (:2442): the mask stays behind it."""
+    name: str
+    channels: int
+    heads: int
+    key_dim: int
+    ff_dim: int
+    blocks: int = 1                # num_blocks (:2426)
+    norm_type: str = "layernorm"   # :2428 (layernorm | masked_layernorm | masked_dyt | masked_batchnorm)
+    epsilon: float = 1e-6          # of the post norm only (:2427); the encoders' layer norms have 1e-6 hard-coded
+    alpha_init: float = 0.5        # MaskedDYT's initial alpha (:2429): training only, the weights carry alpha
+
+    def post_norm(self, block: int) -> Norm:
+        """The post norm of block ``block`` as a :class:`Norm` (``layernorm`` has masked_layernorm's variables)."""
+        kind = "masked_layernorm" if self.norm_type == "layernorm" else self.norm_type
+        return Norm(f"{self.name}/block{block}/post_norm", kind, self.channels, self.epsilon, True)
+
+    def length(self, block: int) -> LengthAttn:
+        return LengthAttn(f"{self.name}/block{block}/length", self.channels, self.heads, self.key_dim, self.ff_dim)
+
+    def frame(self, block: int) -> FrameAttn:
+        return FrameAttn(f"{self.name}/block{block}/frame", self.channels, self.heads, self.key_dim, self.ff_dim, True)
+
+
+#: what the length-attention kernel (csrc/jg_lengthattn.hip) covers
+LENGTHATTN_CHANNELS = (16, 32, 64)
+LENGTHATTN_KEY_DIMS = (4, 8, 16, 32, 64)
+LENGTHATTN_MAX_FF = 256
+_ATTN_REQUIRED = ("embed_dim", "num_heads", "feed_forward_dim")                    # no defaults (layers.py:2207-2212, :2420-2425)
+# the constructors' own arguments plus what keras.layers.Layer.__init__ takes: any other key is an unknown keyword there
+_AXIAL_KEYS = {"embed_dim", "num_heads", "feed_forward_dim", "dropout_rate", "num_blocks", "epsilon", "norm_type",
+               "alpha_init", "name", "dtype", "trainable"}
+_ENCODER_KEYS = {"embed_dim", "num_heads", "feed_forward_dim", "dropout_rate", "attention_axes", "name", "dtype", "trainable"}
+AXIAL_NORM_TYPES = ("layernorm", "masked_layernorm", "masked_dyt", "masked_batchnorm")
+
+
+def length_attn_limit(channels: int, heads: int, ff_dim: int) -> str | None:
+    """Why the length-attention kernel cannot run this size, or None."""
+    if channels not in LENGTHATTN_CHANNELS:
+        return f"embed_dim {channels} (the kernel covers {' / '.join(map(str, LENGTHATTN_CHANNELS))} channels)"
+    if heads < 1 or channels % heads or channels // heads not in LENGTHATTN_KEY_DIMS:
+        return (f"num_heads {heads} at embed_dim {channels} (key_dim = embed_dim / num_heads must be one of "
+                f"{', '.join(map(str, LENGTHATTN_KEY_DIMS))})")
+    if ff_dim % 16 or not 16 <= ff_dim <= LENGTHATTN_MAX_FF:
+        return f"feed_forward_dim {ff_dim} (a multiple of 16 up to {LENGTHATTN_MAX_FF})"
+    return None
+
+
+def _constructor_accepts(cfg: dict, keys: set) -> bool:
+    """Whether the reference's constructor would take this config: the three required arguments are there and no key is
+    an unknown keyword (keras.layers.Layer.__init__ raises on one)."""
+    return all(k in cfg for k in _ATTN_REQUIRED) and not set(cfg) - keys
+
+
+@dataclass
 class ModelPlan:
     vocab: int
     embedding_dim: int
@@ -343,6 +415,43 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
             if why is not None:
                 raise UnsupportedLayer(f"{p}: local_attention with {why}")
             out.append(LocalAttn(p, c, h, c // h, f, window // 2, blocks))
+        elif (name == "transformer_encoder" and _constructor_accepts(cfg, _ENCODER_KEYS)) or \
+                (name == "axial_attention" and _constructor_accepts(cfg, _AXIAL_KEYS)):
+            # builder.py:1155: TransformerEncoder(**config) / AxialAttention(**config); an entry the constructor would not
+            # take (a required argument missing, an unknown keyword) falls through to the generic refusal below
+            if frames is None:
+                raise UnsupportedLayer(f"{p}: {name} needs the (frames, length, channels) tensor of the "
+                                       "representation learner: not supported in a head or on a strand branch")
+            c, h, f = int(cfg["embed_dim"]), int(cfg["num_heads"]), int(cfg["feed_forward_dim"])
+            if c != cin:
+                raise UnsupportedLayer(f"{p}: embed_dim {c} != {cin} incoming channels (the layer's residual adds them, "
+                                       "layers.py:2256)")
+            why = length_attn_limit(c, h, f)
+            if why is not None:
+                raise UnsupportedLayer(f"{p}: {name} with {why}")
+            if name == "transformer_encoder":
+                axes = cfg.get("attention_axes", 2)
+                if axes != 2 and list(axes if isinstance(axes, (list, tuple)) else [axes]) != [2]:
+                    raise UnsupportedLayer(f"{p}: transformer_encoder attention_axes {axes!r} (the kernel attends along the "
+                                           "length axis, attention_axes = 2)")
+                out.append(LengthAttn(p, c, h, c // h, f))
+            else:
+                if frames != 6:
+                    raise UnsupportedLayer(f"{p}: axial_attention over {frames} frames (its frame half attends over the six "
+                                           "reading frames of a translated window)")
+                blocks = int(cfg.get("num_blocks", 1))
+                if blocks < 1:
+                    raise UnsupportedLayer(f"{p}: axial_attention num_blocks {blocks} (at least one block)")
+                nt = str(cfg.get("norm_type", "layernorm")).lower()
+                nt = "layernorm" if nt == "layer_normalization" else nt          # layers.py:2449
+                if nt not in AXIAL_NORM_TYPES:
+                    raise UnsupportedLayer(f"{p}: axial_attention norm_type {nt!r} (layers.py:2457 raises: one of "
+                                           f"{', '.join(AXIAL_NORM_TYPES)})")
+                why = frame_attn_limit(c, h, f)
+                if why is not None:
+                    raise UnsupportedLayer(f"{p}: axial_attention with {why} (its frame half)")
+                out.append(AxialAttn(p, c, h, c // h, f, blocks, nt, float(cfg.get("epsilon", 1e-6)),
+                                     float(cfg.get("alpha_init", 0.5))))
         else:
             raise UnsupportedLayer(
                 f"{p}: layer {name!r} is outside the Conv1D -> norm -> pool -> dense family "
@@ -582,6 +691,13 @@ def weight_shapes(plan: ModelPlan) -> dict[str, tuple]:
                 out.update(frame_attn_weight_shapes(layer))
             elif isinstance(layer, LocalAttn):
                 out.update(local_attn_weight_shapes(layer))
+            elif isinstance(layer, LengthAttn):
+                out.update(length_attn_weight_shapes(layer))
+            elif isinstance(layer, AxialAttn):
+                for j in range(layer.blocks):
+                    out.update(length_attn_weight_shapes(layer.length(j)))
+                    out.update(frame_attn_weight_shapes(layer.frame(j)))
+                    norm(layer.post_norm(j))
         if seq is plan.rep and plan.nmd_merge_mode != "concat":                 # NMDMerge is built behind the rep block's layers
             for i, d in enumerate(plan.nmd_dims):
                 out[f"rep/nmd_merge/proj_{i}/kernel"] = (d, plan.nmd_merge_dim)
@@ -625,6 +741,12 @@ def local_attn_weight_shapes(a: LocalAttn) -> dict[str, tuple]:
         out.update({f"{b}/ln2/gamma": (c,), f"{b}/ln2/beta": (c,), f"{b}/ffn1/kernel": (c, f), f"{b}/ffn1/bias": (f,),
                     f"{b}/ffn2/kernel": (f, c), f"{b}/ffn2/bias": (c,)})
     return out
+
+
+def length_attn_weight_shapes(a: LengthAttn) -> dict[str, tuple]:
+    """Keras variable shapes of one TransformerEncoder: the leaf names and shapes of a CrossFrameAttention layer with its
+    feed-forward half (the two classes hold the same sub-layers under the same names, layers.py:2224-2245, :2321-2345)."""
+    return frame_attn_weight_shapes(FrameAttn(a.name, a.channels, a.heads, a.key_dim, a.ff_dim, True))
 
 
 def frame_attn_flops_per_position(plan: ModelPlan) -> list[tuple[str, int, int]]:

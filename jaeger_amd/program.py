@@ -13,6 +13,11 @@ conv launches with epilogue stages:
   leaves it
 * ``local_attention -> norm -> activation``                   one local-attention op per block (``layers.py:2520-2645``),
   out of place, the mask kept; the norm / activation ride the last block's store
+* ``transformer_encoder -> norm -> activation``               one length-attention op (``layers.py:2206-2280``), out of
+  place, under the incoming mask; no mask leaves it
+* ``axial_attention -> norm -> activation``                   per block a length-attention op (masked in block 0 only), a
+  frame-attention op and an element-wise op with the post norm and the add of the block's input
+  (``layers.py:2400-2517``); the mask kept; the norm / activation ride the last block's element-wise op
 
 Pure host logic (numpy + ctypes structs): unit-tested on CPU.
 """
@@ -24,7 +29,7 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 from . import _lib as L
-from .plan import Act, Conv, Dense, FrameAttn, LocalAttn, ModelPlan, Nmd, Norm, ResBlock, UnsupportedLayer, weight_shapes
+from .plan import Act, AxialAttn, Conv, Dense, FrameAttn, LengthAttn, LocalAttn, ModelPlan, Nmd, Norm, ResBlock, UnsupportedLayer, weight_shapes
 
 _ACT_CODE = {None: L.ACT_NONE, "linear": L.ACT_NONE, "gelu": L.ACT_GELU_TANH, "gelu_erf": L.ACT_GELU_ERF,
              "relu": L.ACT_RELU, "tanh": L.ACT_TANH, "sigmoid": L.ACT_SIGMOID}
@@ -132,6 +137,15 @@ def pack_local_attn(a: LocalAttn, block: int, w: dict[str, np.ndarray]) -> np.nd
     return pack_frame_attn(FrameAttn(p, a.channels, a.heads, a.key_dim, a.ff_dim, True), renamed)
 
 
+LENGTH_ATTN_EPSILON = 1e-6     # both LayerNormalization layers of a TransformerEncoder (layers.py:2224-2226, :2237-2239)
+
+
+def pack_length_attn(a: LengthAttn, w: dict[str, np.ndarray]) -> np.ndarray:
+    """The weights of one TransformerEncoder as the kernel reads them (csrc/jg_lengthattn.hip): :func:`pack_frame_attn`'s
+    fold and layout under the same leaf names."""
+    return pack_frame_attn(FrameAttn(a.name, a.channels, a.heads, a.key_dim, a.ff_dim, True), w)
+
+
 @dataclass
 class Program:
     ops: list            # list[L.JgOp]
@@ -158,7 +172,8 @@ class Program:
             rows.append(f"{kinds[op.kind][3:]:9s} in={op.in_buf} out={op.out_buf} m={op.in_mask}->{op.out_mask} "
                         f"k={op.k} c={op.cin}->{op.cout} s={op.stride} d={op.dilation} [{st}]"
                         + (f" heads={op.k} ff={op.arg}" if op.kind == L.OP_FRAMEATTN else "")
-                        + (f" heads={op.k} ff={op.arg} half_window={op.stride}" if op.kind == L.OP_LOCALATTN else ""))
+                        + (f" heads={op.k} ff={op.arg} half_window={op.stride}" if op.kind == L.OP_LOCALATTN else "")
+                        + (f" heads={op.k} ff={op.arg}" if op.kind == L.OP_LENGTHATTN else ""))
         return rows
 
 
@@ -307,6 +322,15 @@ class _Compiler:
                                    "leaves zeros at positions whose band holds no valid key, where the Keras graph holds "
                                    "values that depend on its version and precision")
 
+    def _length_op(self, a: LengthAttn, in_buf: int, out_buf: int, in_mask: int, out_mask: int, stages: list):
+        op = self._op(L.OP_LENGTHATTN, in_buf=in_buf, out_buf=out_buf, in_mask=in_mask, out_mask=out_mask, k=a.heads,
+                      cin=a.channels, cout=a.channels, arg=a.ff_dim, f0=LENGTH_ATTN_EPSILON,
+                      w_off=self.blob.add(pack_length_attn(a, self.w)))
+        op.n_stages = len(stages)
+        for q, st in enumerate(stages):
+            op.stages[q] = st
+        return op
+
     def _flush_nmd(self, pending: list, buf: int):
         for nmd, slot, mask in pending:
             self.ops.append(self._op(L.OP_NMD_FINAL, in_buf=buf, in_mask=mask, cout=nmd.channels, arg=slot,
@@ -345,6 +369,10 @@ class _Compiler:
         if layers and isinstance(layers[0], LocalAttn):
             raise UnsupportedLayer(f"{layers[0].name}: local_attention directly on the embedding is not supported (the reference's "
                                    "stacks put a conv in front of it; the embedding's rows at invalid codons are not zeros)")
+        if layers and isinstance(layers[0], (LengthAttn, AxialAttn)):
+            kind = "transformer_encoder" if isinstance(layers[0], LengthAttn) else "axial_attention"
+            raise UnsupportedLayer(f"{layers[0].name}: {kind} directly on the embedding is not supported (the reference's "
+                                   "stacks put a conv in front of it)")
         if not layers or not isinstance(layers[0], Conv):
             # A norm / activation / nmd / residual block - or the pool itself - directly on the Embedding output (the
             # reference's own Embedding -> MaskedBatchNorm -> masked max pool case, tests/unit/test_masked_pooling.py:
@@ -509,6 +537,63 @@ class _Compiler:
                     self.bufs.give(buf)
                     buf = out
                 self._emit_ln_tail(layer.name, tail, mask, buf, layer.channels)
+                mask = mask2
+            elif isinstance(layer, LengthAttn):
+                if buf == L.JG_BUF_IDS:
+                    raise UnsupportedLayer(f"{layer.name}: transformer_encoder directly on the embedding is not supported")
+                self._refuse_unmasked_reader(f"{layer.name}: transformer_encoder (a masked query's output is computed from "
+                                             "its input value, and the layer drops the mask)")
+                # TransformerEncoder sees the implicit mask of its input (Keras 3 fills MultiHeadAttention's query_mask /
+                # value_mask from it) and does not set supports_masking: the norm / activation / pool / conv behind it see NO
+                # mask.  They fuse into the op's store; a LayerNorm is cut off into its own op
+                stages = []
+                i, _ = self._fuse_tail(layers, i + 1, stages, L.JG_BUF_NONE, layer.channels, pending)
+                if pending:
+                    raise UnsupportedLayer(f"{layer.name}: an nmd tap directly behind transformer_encoder is not supported "
+                                           "(the op's store carries no partial sums)")
+                tail = []
+                for j, st in enumerate(stages):
+                    if st.kind == L.ST_LN:
+                        stages, tail = stages[:j], stages[j:]
+                        break
+                out = self.bufs.take()
+                self.ops.append(self._length_op(layer, buf, out, mask, L.JG_BUF_NONE, stages))
+                self._emit_ln_tail(layer.name, tail, L.JG_BUF_NONE, out, layer.channels)
+                self.bufs.give(buf)
+                self.masks.give(mask)
+                buf, mask = out, L.JG_BUF_NONE
+            elif isinstance(layer, AxialAttn):
+                if buf == L.JG_BUF_IDS:
+                    raise UnsupportedLayer(f"{layer.name}: axial_attention directly on the embedding is not supported")
+                self._refuse_unmasked_reader(f"{layer.name}: axial_attention (a masked query's output is computed from its "
+                                             "input value, and its frame half attends over all six frames of a position)")
+                # per block (layers.py:2485-2501): r = x; x = length(x) - under the layer's incoming mask in block 0 only:
+                # from block 1 on x is the result of a tensor op inside call() and carries no implicit mask -; x = frame(x),
+                # unmasked; x = norm(x) (masked_layernorm / masked_dyt: with the incoming mask, in every block) + r.  The layer
+                # keeps the mask (supports_masking, :2442); the block-input slot stays taken until the add
+                for j in range(layer.blocks):
+                    la, fa, norm = layer.length(j), layer.frame(j), layer.post_norm(j)
+                    t1 = self.bufs.take()
+                    lm = mask if j == 0 else L.JG_BUF_NONE
+                    self.ops.append(self._length_op(la, buf, t1, lm, lm, []))
+                    t2 = self.bufs.take()
+                    self.ops.append(self._op(L.OP_FRAMEATTN, in_buf=t1, out_buf=t2, in_mask=L.JG_BUF_NONE, out_mask=L.JG_BUF_NONE,
+                                             k=fa.heads, cin=fa.channels, cout=fa.channels, arg=fa.ff_dim, f0=FRAME_ATTN_EPSILON,
+                                             w_off=self.blob.add(pack_frame_attn(fa, self.w))))
+                    self.bufs.give(t1)
+                    masked_norm = layer.norm_type in ("masked_layernorm", "masked_dyt") and mask != L.JG_BUF_NONE
+                    stages = [self._norm_stage(norm, masked_norm), self._stage(L.ST_ADD, arg=buf)]
+                    mask2 = mask
+                    if j == layer.blocks - 1:
+                        i, mask2 = self._fuse_tail(layers, i + 1, stages, mask, layer.channels, pending)
+                        if pending:
+                            raise UnsupportedLayer(f"{layer.name}: an nmd tap directly behind axial_attention is not supported "
+                                                   "(the element-wise op that closes the layer carries no partial sums)")
+                    self._emit_ln_tail(layer.name, stages, mask, t2, layer.channels)
+                    self.bufs.give(buf)
+                    buf = t2
+                if mask2 != mask:
+                    self.masks.give(mask)
                 mask = mask2
             elif isinstance(layer, Nmd):
                 raise UnsupportedLayer("an nmd layer must directly follow a conv or residual block")

@@ -16,7 +16,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .plan import Conv, Dense, FrameAttn, LocalAttn, ModelPlan, Nmd, Norm, ResBlock, weight_shapes
+from .plan import AxialAttn, Conv, Dense, FrameAttn, LengthAttn, LocalAttn, ModelPlan, Nmd, Norm, ResBlock, weight_shapes
 
 
 def random_weights(plan: ModelPlan, seed: int = 38341) -> dict[str, np.ndarray]:
@@ -49,15 +49,16 @@ def load_npz(path) -> dict[str, np.ndarray]:
 
 
 def attention_layers(plan: ModelPlan) -> list[str]:
-    """Names of the plan's cross_frame_attention and local_attention layers."""
+    """Names of the plan's cross_frame_attention, local_attention, transformer_encoder and axial_attention layers."""
     return [l.name for seq in (plan.rep, plan.classifier, plan.reliability or []) for l in seq
-            if isinstance(l, (FrameAttn, LocalAttn))]
+            if isinstance(l, (FrameAttn, LocalAttn, LengthAttn, AxialAttn))]
 
 
 def attention_kinds(plan: ModelPlan) -> str:
     """The YAML names of the attention layer kinds the plan holds, for the refusals that name them."""
     layers = [l for seq in (plan.rep, plan.classifier, plan.reliability or []) for l in seq]
-    kinds = [name for cls, name in ((FrameAttn, "cross_frame_attention"), (LocalAttn, "local_attention"))
+    kinds = [name for cls, name in ((FrameAttn, "cross_frame_attention"), (LocalAttn, "local_attention"),
+                                          (LengthAttn, "transformer_encoder"), (AxialAttn, "axial_attention"))
              if any(isinstance(l, cls) for l in layers)]
     return " / ".join(kinds)
 
