@@ -88,6 +88,20 @@ typedef enum {
                           (inside an axial layer, which keeps the mask) or JG_BUF_NONE (a stand-alone encoder drops it).
                           stages: bias / batch norm / unmasked DyT / activation.  C 16, 32 or 64, key_dim 4 .. 64, arg a
                           multiple of 16 up to 256: jg_model_create refuses other sizes with the reason */
+  JG_OP_HYENA = 16,     /* one HyenaBlock (nnlib/v2/layers.py:2724-3153): in_buf -> out_buf (never the same slot), f32 rows (frames, L, C)
+                          per window, rows independent.  With in_mask a mask slot: x' = x m; n = LayerNorm(x') m; p_j = n W_j for
+                          j = 0 .. order; z = p_0; z = p_(i+1) * causal_conv(z, h_i) for i < order, causal_conv(z, h)[t, c] =
+                          sum over s <= t of h[t - s, c] z[s, c]; y = z (W_o + b_o with the output projection); out = (y + x') m:
+                          masked positions are exact zeros.  in_mask = JG_BUF_NONE: every multiply by m is absent.  out_mask =
+                          in_mask (the layer keeps the mask).  cin = cout = C, k = order, arg = JG_HYENA_OUT_PROJ (1) |
+                          JG_HYENA_NORMALIZE (2), stride = rows R of the filter table (`dilation` stays 1), f0 = epsilon of the
+                          layer norm (1e-6).  w_off = wp [order + 1][C][C] (input channel, output channel; the norm's gamma folded
+                          in) | bp [order + 1][C] (beta @ W_j) | with JG_HYENA_OUT_PROJ wo [C][C] | bo [C] | the filter table h
+                          [order][R][C], indexed by the LAG t - s | with JG_HYENA_NORMALIZE ssq [order][R][C], ssq[i][t][c] = sum
+                          over s <= t of h[i][s][c]^2: a call at L positions scales the convolution by 1 / sqrt(ssq[i][L - 1][c]),
+                          by 0 where that is 0 (divide_no_nan).  stages: bias / batch norm / unmasked DyT / activation.  C 16, 32
+                          or 64, order 1 .. 4, R >= 1: jg_model_create refuses other sizes with the reason; a forward whose rows
+                          are longer than R is refused with JG_ERR_UNSUPPORTED before any launch */
   JG_OP_STRANDS = 10   /* a branched (shared-weight) model over the k strands of a nucleotide input: every strand is a
                           program row of its own (ids (W, k, L), one frame per row); arg = how the strands' predictions
                           merge (jg_merge_kind); the embedding output is their average.  builder.py:1195-1266, :776-791 */
@@ -344,6 +358,10 @@ int jg_localattn_tile(void);
  * LDS at a time - row lengths around them are where a ragged last tile and a ragged last chunk lie */
 int jg_lengthattn_tile(void);
 int jg_lengthattn_chunk(void);
+/* the hyena kernels (JG_OP_HYENA): positions of one workgroup, and earlier positions that go through LDS at a time (one
+ * partial sum each) - row lengths around them are where a ragged last tile and a second chunk lie */
+int jg_hyena_tile(void);
+int jg_hyena_chunk(void);
 
 /* Box calibration (bench.py's `box` object; no counterpart in the reference): about `seconds` (0 < seconds <= 30) of
  * back-to-back launches of a bare v_mfma_f32_32x32x16_f16 loop on random register operands, two waves per SIMD on every

@@ -270,6 +270,8 @@ struct jg_model {
   bool needs_cvt = false;         // the program holds F16S <-> f32 layout conversions (needs the scratch tensor)
   float *cvt_scratch = nullptr;
   int64_t cvt_cap = 0;
+  float *hy_scratch = nullptr;    // p_0 .. p_order of the hyena ops (jg_hyena.hip), sized by the shape walk
+  int64_t hy_cap = 0;             // bytes
   std::string f16_reason;         // why the fast path is unavailable
   int *d_overflow = nullptr;
   float *d_w = nullptr;

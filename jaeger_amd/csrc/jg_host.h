@@ -13,6 +13,7 @@
 #include "jg_frameattn.h"
 #include "jg_localattn.h"
 #include "jg_lengthattn.h"
+#include "jg_hyena.h"
 
 #pragma GCC visibility push(hidden)
 // ---- shapes: jg_shape_walk (jg_model.hip) is the only place that computes them -------------------------------------
@@ -24,6 +25,7 @@ struct OpShape {                // op i at l positions per row
   int L_out = 0, pad_left = 0;  // CONV / MASK geometry (MAXPOOL1D: L_out)
   int m_in = 0, m_out = 0;      // MASK / EMBED: positions per frame of the mask read and written
   int vec_need = 0;             // floats of out_vec this op needs (vec_off + its width)
+  int64_t scratch = 0;          // HYENA: floats of the projection scratch per window
   Shape cvt[3];                 // the tensors converted in front of the op (ConvHPrep::cvt_slot), as they are then
 };
 int jg_shape_walk(const jg_model *m, int l, std::vector<OpShape> &shp);
@@ -45,6 +47,7 @@ enum Place {
   PL_LOCALATTN,    // local attention: jg_localattn.hip (f32 rows, out of place, the mask kept)
   PL_ORDINARY,     // the op's own kernel
   PL_LENGTHATTN,   // full-row length attention: jg_lengthattn.hip (f32 rows, out of place)
+  PL_HYENA,        // hyena block: jg_hyena.hip (f32 rows, out of place, 2 + order launches through the projection scratch)
 };
 struct PlaceCtx {  // what placement depends on besides the model
   int prec;        // 0 exact f32, 1 split-f16

@@ -25,7 +25,7 @@ static int validate_program(const jg_model *m) {
     auto slot_ok = [](int s, bool allow_ids) {
       return (s >= 0 && s < JG_MAX_BUFS) || s == JG_BUF_NONE || (allow_ids && s == JG_BUF_IDS);
     };
-    JG_REQUIRE(op.kind >= JG_OP_CONV && op.kind <= JG_OP_LENGTHATTN, JG_ERR_INVALID,
+    JG_REQUIRE(op.kind >= JG_OP_CONV && op.kind <= JG_OP_HYENA, JG_ERR_INVALID,
                "op %zu: unknown kind %d", i, op.kind);
     if (op.kind == JG_OP_VECMAX)
       JG_REQUIRE(op.in_vec >= 0 && op.out_vec >= 0 && op.in_vec != op.out_vec && op.k >= 1 && op.cout >= 1 && op.vec_off >= 0,
@@ -124,6 +124,26 @@ static int validate_program(const jg_model *m) {
         const int kd = op.stages[s].kind;
         JG_REQUIRE(kd == JG_ST_BIAS || kd == JG_ST_BN || kd == JG_ST_ACT || (kd == JG_ST_DYT && op.stages[s].arg == 0), JG_ERR_UNSUPPORTED,
                    "op %zu stage %d: only bias / batch norm / unmasked DyT / activation stages fuse behind length attention (kind %d)", i, s, kd);
+      }
+    }
+    if (op.kind == JG_OP_HYENA) {
+      // cin = cout = channels, k = order, arg = flags, stride = rows of the filter table, f0 = the layer norm's epsilon
+      JG_REQUIRE(op.in_buf >= 0 && op.out_buf >= 0 && op.cin == op.cout && op.f0 > 0.f && op.dilation == 1, JG_ERR_INVALID,
+                 "op %zu: a hyena op reads and writes an activation slot of cin = cout channels", i);
+      JG_REQUIRE(op.in_buf != op.out_buf, JG_ERR_INVALID, "op %zu: a hyena op cannot run in place", i);
+      JG_REQUIRE((op.in_mask >= 0 || op.in_mask == JG_BUF_NONE) && op.out_mask == op.in_mask, JG_ERR_INVALID,
+                 "op %zu: a hyena op keeps its mask (out_mask = in_mask, a mask slot or none)", i);
+      JG_REQUIRE((op.arg & ~(JG_HYENA_OUT_PROJ | JG_HYENA_NORMALIZE)) == 0, JG_ERR_INVALID, "op %zu: hyena flags %d", i, op.arg);
+      char why[160];
+      JG_REQUIRE(jg_hyena_supports(op.cin, op.k, op.stride, why, sizeof(why)), JG_ERR_UNSUPPORTED, "op %zu: hyena with %s", i, why);
+      JG_REQUIRE(m->ops.back().kind != JG_OP_STRANDS, JG_ERR_UNSUPPORTED,
+                 "op %zu: hyena needs the frame rows of a translated window (not a strand program)", i);
+      JG_REQUIRE(off_ok(op.w_off, jg_hyena_blob_floats(op.cin, op.k, op.stride, op.arg)), JG_ERR_INVALID,
+                 "op %zu: hyena weights and filter table outside the weight blob", i);
+      for (int s = 0; s < op.n_stages; ++s) {
+        const int kd = op.stages[s].kind;
+        JG_REQUIRE(kd == JG_ST_BIAS || kd == JG_ST_BN || kd == JG_ST_ACT || (kd == JG_ST_DYT && op.stages[s].arg == 0), JG_ERR_UNSUPPORTED,
+                   "op %zu stage %d: only bias / batch norm / unmasked DyT / activation stages fuse behind a hyena op (kind %d)", i, s, kd);
       }
     }
     if (op.kind == JG_OP_DENSE) {
@@ -237,6 +257,19 @@ int jg_shape_walk(const jg_model *m, int l, std::vector<OpShape> &shp) {
         }
         r.out = r.in;
         break;
+      case JG_OP_HYENA:
+        JG_REQUIRE(r.in.C == op.cin && r.in.frames == m->id_frames, JG_ERR_INVALID,
+                   "op %zu: hyena over %d channels expects (%d, L, %d) rows, input is (%d, L, %d)", i, op.cin, m->id_frames, op.cin, r.in.frames, r.in.C);
+        if (op.in_mask >= 0) {
+          r.m_in = mL[op.in_mask];
+          JG_REQUIRE(r.m_in == r.in.L, JG_ERR_INVALID, "op %zu: hyena over rows of %d positions with a mask of %d", i, r.in.L, r.m_in);
+        }
+        JG_REQUIRE(r.in.L <= op.stride, JG_ERR_UNSUPPORTED,
+                   "op %zu: hyena over rows of %d positions, the layer's filter table holds %d (seq_len of the layer, or the %d rows a program carries)",
+                   i, r.in.L, op.stride, op.stride);
+        r.scratch = (int64_t)r.in.frames * jg_hyena_row_scratch(op.cin, op.k, r.in.L);
+        r.out = r.in;
+        break;
       case JG_OP_MAXPOOL1D:
         r.L_out = r.in.L / 2;
         JG_REQUIRE(r.L_out > 0, JG_ERR_INVALID, "op %zu: maxpool output empty", i);
@@ -295,12 +328,14 @@ static void fold_shapes(const jg_model *m, int l, const std::vector<OpShape> &sh
     }
     if (op.kind == JG_OP_LENGTHATTN)      // dense products (k and v once per query tile) plus 4 L^2 C of scores and context
       fl += jg_lengthattn_row_flops(op.cin, op.arg, r.in.L) * (double)r.in.frames;
+    if (op.kind == JG_OP_HYENA)           // the projections and 2 x order x C x L (L + 1) / 2 of the convolutions
+      fl += jg_hyena_row_flops(op.cin, op.k, op.arg, r.in.L) * (double)r.in.frames;
     if (r.m_out > 0) msk_elems[op.out_mask] = std::max<int64_t>(msk_elems[op.out_mask], (int64_t)m->id_frames * r.m_out);
     if (r.vec_need > 0) vec_w[op.out_vec] = std::max(vec_w[op.out_vec], r.vec_need);
     if (r.out.frames == 0 || (tab && (int)i == m->tab_conv)) continue;      // (table net: the activation never exists)
     // (+ one position for an odd row: a phase-split tensor holds two phases of (L + 1) / 2 positions)
     const bool ps_room = op.kind == JG_OP_CONV || op.kind == JG_OP_EMBED || op.kind == JG_OP_FRAMEATTN || op.kind == JG_OP_LOCALATTN ||
-                         op.kind == JG_OP_LENGTHATTN;
+                         op.kind == JG_OP_LENGTHATTN || op.kind == JG_OP_HYENA;
     const Shape &t = r.out;
     act_elems[op.out_buf] = std::max<int64_t>(act_elems[op.out_buf], (int64_t)t.frames * (t.L + (ps_room ? t.L & 1 : 0)) * t.C);
     const int tiles = std::max((t.L + 63) / 64, 8 * ((t.L + 255) / 256));
@@ -352,6 +387,14 @@ extern "C" int jg_model_describe(const jg_model *m, char *buf, int64_t cap) {
     if (op.kind == JG_OP_LENGTHATTN) {
       snprintf(line, sizeof(line), "op %zu: length attention c=%d heads=%d key_dim=%d ff=%d %s -> one launch, exact-f32 matrix cores (dense), vector ALUs (scores, context), f32 rows%s\n",
                i, op.cin, op.k, op.cin / op.k, op.arg, op.in_mask >= 0 ? "masked queries and keys" : "no mask",
+               (m->f16_eligible && m->hprep[i].n_cvt > 0) ? " (F16S -> f32 conversion in front)" : "");
+      out += line;
+      continue;
+    }
+    if (op.kind == JG_OP_HYENA) {
+      snprintf(line, sizeof(line), "op %zu: hyena c=%d order=%d table_rows=%d%s%s %s -> %d launches: projections on the exact-f32 matrix cores, causal convolutions on the vector ALUs, f32 rows%s\n",
+               i, op.cin, op.k, op.stride, (op.arg & JG_HYENA_OUT_PROJ) ? " output_projection" : "", (op.arg & JG_HYENA_NORMALIZE) ? " filter_normalize" : "",
+               op.in_mask >= 0 ? "masked" : "no mask", 2 + op.k,
                (m->f16_eligible && m->hprep[i].n_cvt > 0) ? " (F16S -> f32 conversion in front)" : "");
       out += line;
       continue;
@@ -492,6 +535,7 @@ extern "C" int jg_model_destroy(jg_model *m) {
   if (m->tab_table) (void)hipFree(m->tab_table);
   if (m->tab_bias) (void)hipFree(m->tab_bias);
   if (m->d_w) (void)hipFree(m->d_w);
+  if (m->hy_scratch) (void)hipFree(m->hy_scratch);
   if (m->d_ids) (void)hipFree(m->d_ids);
   if (m->d_counts) (void)hipFree(m->d_counts);
   if (m->d_win) (void)hipFree(m->d_win);
@@ -520,6 +564,13 @@ extern "C" int jg_model_destroy(jg_model *m) {
 int jg_ensure_workspace(jg_model *m, int64_t chunk, int l, const std::vector<OpShape> &shp) {
   int64_t nmd_elems[JG_MAX_BUFS];
   fold_shapes(m, l, shp, m->act_elems, m->msk_elems, nmd_elems, m->vec_w, nullptr);
+  int64_t hy_need = 0;                 // the hyena ops' projection scratch: kept apart from the slots, grown on demand
+  for (const OpShape &r : shp) hy_need = std::max(hy_need, chunk * r.scratch * (int64_t)sizeof(float));
+  if (hy_need > m->hy_cap) {
+    JG_HIP(hipStreamSynchronize(m->e->stream));
+    int rc = grow(&m->hy_scratch, &m->hy_cap, hy_need);
+    if (rc != JG_OK) return rc;
+  }
   bool fits = true;
   for (int i = 0; i < JG_MAX_BUFS; ++i) {
     m->nmd_part_elems[i] = nmd_elems[i];
@@ -574,7 +625,7 @@ const char *jg_tap_refusal(const jg_model *m, size_t i, const PlaceCtx &c, int l
   const jg_op &op = m->ops[i];
   if (op.kind != JG_OP_CONV && op.kind != JG_OP_MASK && op.kind != JG_OP_ELTWISE && op.kind != JG_OP_EMBED &&
       op.kind != JG_OP_MAXPOOL1D && op.kind != JG_OP_FRAMESUM && op.kind != JG_OP_FRAMEATTN && op.kind != JG_OP_LOCALATTN &&
-      op.kind != JG_OP_LENGTHATTN) {
+      op.kind != JG_OP_LENGTHATTN && op.kind != JG_OP_HYENA) {
     snprintf(why, cap, "op %zu (kind %d) writes a vector or nothing - pool, dense and vector results are outputs already", i, op.kind);
     return why;
   }
@@ -630,7 +681,7 @@ int jg_tap_copy(jg_model *m, size_t i, const OpShape &r, const PlaceCtx &c, int 
   if (pl == PL_CONV_F16 && m->tap_flat) v |= JG_TAP_WINDOW_PACKED;
   if (f16_conv && hp.d_lut != nullptr) v |= JG_TAP_TABLE_LOOKUP;
   if (f16_conv && hp.cw != 128) v |= JG_TAP_NARROW;
-  if (op.kind == JG_OP_FRAMEATTN || op.kind == JG_OP_LOCALATTN || op.kind == JG_OP_LENGTHATTN) v |= JG_TAP_EXACT_F32;      // one arithmetic (exact-f32 matrix cores), one layout (f32 rows)
+  if (op.kind == JG_OP_FRAMEATTN || op.kind == JG_OP_LOCALATTN || op.kind == JG_OP_LENGTHATTN || op.kind == JG_OP_HYENA) v |= JG_TAP_EXACT_F32;      // one arithmetic (exact-f32 matrix cores), one layout (f32 rows)
   m->tap_variant |= v;
   float *out = reinterpret_cast<float *>(dst + m->tap_row0 * per_row);
   if (!f16s) {

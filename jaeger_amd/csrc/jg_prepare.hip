@@ -63,7 +63,7 @@ int jg_prepare_small(jg_model *m, const float *weights) {
   for (size_t i = (size_t)pool_op + 1; i < m->ops.size(); ++i) {
     const int k = m->ops[i].kind;
     if (k == JG_OP_CONV || k == JG_OP_MASK || k == JG_OP_POOL || k == JG_OP_ELTWISE || k == JG_OP_MAXPOOL1D ||
-        k == JG_OP_FRAMESUM || k == JG_OP_NMD_FINAL || k == JG_OP_FRAMEATTN || k == JG_OP_LOCALATTN || k == JG_OP_LENGTHATTN)
+        k == JG_OP_FRAMESUM || k == JG_OP_NMD_FINAL || k == JG_OP_FRAMEATTN || k == JG_OP_LOCALATTN || k == JG_OP_LENGTHATTN || k == JG_OP_HYENA)
       return JG_OK;
   }
   JgSmallNet *sn = new JgSmallNet();
@@ -608,7 +608,7 @@ int jg_prepare_f16(jg_model *m, const float *weights) {
   auto reads = [&](size_t j, int buf) {
     const jg_op &o = m->ops[j];
     if ((o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-         o.kind == JG_OP_POOL || o.kind == JG_OP_NMD_FINAL || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN) && o.in_buf == buf)
+         o.kind == JG_OP_POOL || o.kind == JG_OP_NMD_FINAL || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN || o.kind == JG_OP_HYENA) && o.in_buf == buf)
       return o.kind != JG_OP_NMD_FINAL;               // (NMD_FINAL only takes the slot's shape)
     if (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE)
       for (int q = 0; q < o.n_stages; ++q)
@@ -618,7 +618,7 @@ int jg_prepare_f16(jg_model *m, const float *weights) {
   auto writes = [&](size_t j, int buf) {
     const jg_op &o = m->ops[j];
     return (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-            o.kind == JG_OP_EMBED || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN) &&
+            o.kind == JG_OP_EMBED || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN || o.kind == JG_OP_HYENA) &&
            o.out_buf == buf;
   };
   bool cvt_overflow = false;
@@ -681,6 +681,7 @@ int jg_prepare_f16(jg_model *m, const float *weights) {
           if (op.stages[q].kind == JG_ST_ADD) need(i, op.stages[q].arg, true);
         is_f32[op.out_buf] = true;
         break;
+      case JG_OP_HYENA:
       case JG_OP_LENGTHATTN:
       case JG_OP_LOCALATTN:
       case JG_OP_FRAMEATTN:                             // f32 rows in and out: an F16S producer is converted in front of it
@@ -727,7 +728,7 @@ int jg_plan_phase_split(jg_model *m, const float *weights) {
   auto reads_buf = [&](size_t j, int buf) {
     const jg_op &o = m->ops[j];
     if ((o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-         o.kind == JG_OP_POOL || o.kind == JG_OP_NMD_FINAL || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN) && o.in_buf == buf)
+         o.kind == JG_OP_POOL || o.kind == JG_OP_NMD_FINAL || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN || o.kind == JG_OP_HYENA) && o.in_buf == buf)
       return true;
     if (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE)
       for (int q = 0; q < o.n_stages; ++q)
@@ -737,7 +738,7 @@ int jg_plan_phase_split(jg_model *m, const float *weights) {
   auto writes_buf = [&](size_t j, int buf) {
     const jg_op &o = m->ops[j];
     return (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-            o.kind == JG_OP_EMBED || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN) &&
+            o.kind == JG_OP_EMBED || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN || o.kind == JG_OP_HYENA) &&
            o.out_buf == buf;
   };
   for (size_t p = 0; p < n; ++p) {
@@ -831,7 +832,7 @@ int jg_plan_resblocks(jg_model *m, const float *weights) {
   auto reads_buf = [&](size_t j, int buf) {
     const jg_op &o = m->ops[j];
     if ((o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-         o.kind == JG_OP_POOL || o.kind == JG_OP_NMD_FINAL || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN) && o.in_buf == buf)
+         o.kind == JG_OP_POOL || o.kind == JG_OP_NMD_FINAL || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN || o.kind == JG_OP_HYENA) && o.in_buf == buf)
       return true;
     if (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE)
       for (int q = 0; q < o.n_stages; ++q)
@@ -841,7 +842,7 @@ int jg_plan_resblocks(jg_model *m, const float *weights) {
   auto writes_buf = [&](size_t j, int buf) {
     const jg_op &o = m->ops[j];
     return (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-            o.kind == JG_OP_EMBED || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN) &&
+            o.kind == JG_OP_EMBED || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN || o.kind == JG_OP_HYENA) &&
            o.out_buf == buf;
   };
   // bias / batch-norm stages in front of the first other stage, folded with the weights' un-scale (as prepare_f16 does)

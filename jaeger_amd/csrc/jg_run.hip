@@ -44,6 +44,7 @@ Place jg_place_op(const jg_model *m, size_t i, const PlaceCtx &c) {
   }
   if (op.kind == JG_OP_LOCALATTN) return PL_LOCALATTN;
   if (op.kind == JG_OP_LENGTHATTN) return PL_LENGTHATTN;
+  if (op.kind == JG_OP_HYENA) return PL_HYENA;
   if (op.kind == JG_OP_POOL && c.prec == 1 && m->pool_fused_by[i] >= 0) return PL_POOL_FUSED;
   return PL_ORDINARY;
 }
@@ -460,6 +461,28 @@ static int launch_lengthattn(jg_model *m, size_t i, const OpShape &r, int nw, hi
   return jg_launch_lengthattn(m->e, a, s);
 }
 
+// one hyena block: out of place, validity from the op's mask slot (left as it is); p_0 .. p_order go through the model's
+// projection scratch (jg_ensure_workspace sized it from the shape walk).  No profiling class of its own
+// (scripts/hyena_perf.py times it with events around whole programs)
+static int launch_hyena(jg_model *m, size_t i, const OpShape &r, int nw, hipStream_t s) {
+  const jg_op &op = m->ops[i];
+  JG_REQUIRE((int64_t)nw * r.scratch * (int64_t)sizeof(float) <= m->hy_cap, JG_ERR_INVALID, "op %zu: hyena scratch of %lld bytes, %lld needed",
+             i, (long long)m->hy_cap, (long long)((int64_t)nw * r.scratch * (int64_t)sizeof(float)));
+  JgHyenaArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = m->act[op.in_buf];
+  a.y = m->act[op.out_buf];
+  a.mask = op.in_mask >= 0 ? m->msk[op.in_mask] : nullptr;
+  a.w = m->d_w + op.w_off;
+  a.scratch = m->hy_scratch;
+  a.rows = nw * r.in.frames; a.L = r.in.L; a.tiles = (r.in.L + JG_HYENA_TILE - 1) / JG_HYENA_TILE;
+  a.C = op.cin; a.order = op.k; a.table_rows = op.stride;
+  a.out_proj = (op.arg & JG_HYENA_OUT_PROJ) != 0; a.normalize = (op.arg & JG_HYENA_NORMALIZE) != 0;
+  a.eps = op.f0;
+  resolve_stages(m, op, a.st, &a.n_stages);
+  return jg_launch_hyena(m->e, a, s);
+}
+
 static int launch_nmd_final(jg_model *m, size_t i, const OpShape &r, int nw, hipStream_t s) {
   // op.arg = partial slot, in_mask = mask the tap used, cout = channels,
   // in_buf = activation slot whose shape gives the position count
@@ -549,6 +572,7 @@ static int run_chunk(jg_model *m, const std::vector<OpShape> &shp, const uint8_t
         break;
       case PL_LOCALATTN: rc = launch_localattn(m, i, r, nw, s); break;
       case PL_LENGTHATTN: rc = launch_lengthattn(m, i, r, nw, s); break;
+      case PL_HYENA: rc = launch_hyena(m, i, r, nw, s); break;
       case PL_ORDINARY: rc = launch_ordinary(m, i, r, d_ids, nw, s); break;
     }
     if (rc != JG_OK) return rc;

@@ -6,7 +6,8 @@ in ``nnlib/builder.py`` (``build_fragment_classifier`` :442-838,
 :1697-1714).  This module resolves the same section into a flat, fully
 defaulted plan (every default below cites the constructor it comes from) that
 ``program.py`` compiles for the MI355X engine.  Layers outside the conv family
-(attention, LSTM, Hyena, gated pooling ...) raise :class:`UnsupportedLayer`.
+(multi-scale conv, LSTM, gated pooling ...) raise :class:`UnsupportedLayer`; the attention layers and ``hyena_block``
+are plan nodes of their own.
 
 Canonical weight names (shared with the loaders in ``weights.py``):
 ``embedding/embeddings``; ``rep/<i>/{kernel,bias,gamma,beta,moving_mean,
@@ -226,6 +227,50 @@ def length_attn_limit(channels: int, heads: int, ff_dim: int) -> str | None:
                 f"{', '.join(map(str, LENGTHATTN_KEY_DIMS))})")
     if ff_dim % 16 or not 16 <= ff_dim <= LENGTHATTN_MAX_FF:
         return f"feed_forward_dim {ff_dim} (a multiple of 16 up to {LENGTHATTN_MAX_FF})"
+    return None
+
+
+@dataclass
+class Hyena:
+    """One HyenaBlock (layers.py:3023-3153) on the rows of the (frames, length, channels) tensor: ``x * m`` -> LayerNorm
+    (eps 1e-6, :3075) ``* m`` -> HyenaOperator (:2937-3002: ``order + 1`` bias-free projections, ``order`` gated causal long
+    convolutions whose filters come from HyenaFilter, :2766-2915) -> with ``output_projection`` Dense(channels) -> plus the
+    masked input, ``* m`` (:3103-3133).  The layer sets supports_masking (:3072): the mask stays behind it, and masked
+    positions are exact zeros."""
+    name: str
+    channels: int
+    order: int = 2                 # :3051
+    filter_hidden: int = 32        # :3052
+    filter_layers: int = 2         # :3053
+    filter_activation: str | None = "gelu"   # :3054
+    filter_normalize: bool = False # :3057
+    output_projection: bool = False   # :3056
+    seq_len: int | None = None     # :3050: rows of the stored positional encoding; a longer call fails in the reference
+
+
+#: what the hyena kernels (csrc/jg_hyena.hip) and the host's filter table (program.py) cover
+HYENA_CHANNELS = (16, 32, 64)
+HYENA_MAX_ORDER = 4
+HYENA_PE_DIM = 16                  # HyenaFilter's pe_dim default (:2797); HyenaOperator never passes another
+HYENA_ACTIVATIONS = ("gelu", "sin", "relu", "tanh", "sigmoid", "silu", "swish", "linear")
+# the constructor's own arguments (:3047-3059) plus what keras.layers.Layer.__init__ takes; kernel_regularizer_w is the
+# builder's spelling of the regulariser's weight
+_HYENA_KEYS = {"dim", "seq_len", "order", "filter_hidden", "filter_layers", "filter_activation", "dropout",
+               "output_projection", "filter_normalize", "kernel_regularizer", "kernel_regularizer_w", "name", "dtype",
+               "trainable"}
+
+
+def hyena_limit(channels: int, order: int, filter_layers: int, activation) -> str | None:
+    """Why the hyena kernels / the host's filter table cannot run this layer, or None."""
+    if channels not in HYENA_CHANNELS:
+        return f"dim {channels} (the kernels cover {' / '.join(map(str, HYENA_CHANNELS))} channels)"
+    if not 1 <= order <= HYENA_MAX_ORDER:
+        return f"order {order} (the kernels cover orders 1 to {HYENA_MAX_ORDER})"
+    if filter_layers < 1:
+        return f"filter_layers {filter_layers} (the filter network needs at least one Dense layer)"
+    if activation is not None and str(activation).lower() not in HYENA_ACTIVATIONS:
+        return (f"filter_activation {activation!r} (the host tables the filter with one of "
+                f"{', '.join(HYENA_ACTIVATIONS)} or none)")
     return None
 
 
@@ -452,6 +497,31 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
                     raise UnsupportedLayer(f"{p}: axial_attention with {why} (its frame half)")
                 out.append(AxialAttn(p, c, h, c // h, f, blocks, nt, float(cfg.get("epsilon", 1e-6)),
                                      float(cfg.get("alpha_init", 0.5))))
+        elif name == "hyena_block" and "dim" in cfg and not set(cfg) - _HYENA_KEYS:
+            # builder.py:1155: HyenaBlock(**config); an entry without `dim` or with an unknown keyword raises in the reference's
+            # constructor and falls through to the generic refusal below.  dropout and the regulariser matter in training only
+            if frames is None:
+                raise UnsupportedLayer(f"{p}: hyena_block needs the (frames, length, channels) tensor of the "
+                                       "representation learner: not supported in a head or on a strand branch")
+            c, order = int(cfg["dim"]), int(cfg.get("order", 2))
+            if c != cin:
+                raise UnsupportedLayer(f"{p}: dim {c} != {cin} incoming channels (the layer's residual adds them, "
+                                       "layers.py:3129)")
+            fl, act = int(cfg.get("filter_layers", 2)), cfg.get("filter_activation", "gelu")
+            why = hyena_limit(c, order, fl, act)
+            if why is not None:
+                raise UnsupportedLayer(f"{p}: hyena_block with {why}")
+            seq_len = cfg.get("seq_len")
+            if seq_len is not None and int(seq_len) < 1:
+                raise UnsupportedLayer(f"{p}: hyena_block seq_len {seq_len} (a positive number of positions, or none)")
+            nxt = layers[i + 1] if i + 1 < len(layers) else {}
+            if str(nxt.get("name", "")).lower() == "nmd" or (nxt.get("config") or {}).get("return_nmd"):
+                raise UnsupportedLayer(f"{p}: an nmd tap directly behind hyena_block is not supported "
+                                       "(the op's store carries no partial sums)")
+            out.append(Hyena(p, c, order, int(cfg.get("filter_hidden", 32)), fl,
+                             None if act is None or str(act).lower() == "linear" else str(act).lower(),
+                             bool(cfg.get("filter_normalize", False)), bool(cfg.get("output_projection", False)),
+                             None if seq_len is None else int(seq_len)))
         else:
             raise UnsupportedLayer(
                 f"{p}: layer {name!r} is outside the Conv1D -> norm -> pool -> dense family "
@@ -693,6 +763,8 @@ def weight_shapes(plan: ModelPlan) -> dict[str, tuple]:
                 out.update(local_attn_weight_shapes(layer))
             elif isinstance(layer, LengthAttn):
                 out.update(length_attn_weight_shapes(layer))
+            elif isinstance(layer, Hyena):
+                out.update(hyena_weight_shapes(layer))
             elif isinstance(layer, AxialAttn):
                 for j in range(layer.blocks):
                     out.update(length_attn_weight_shapes(layer.length(j)))
@@ -747,6 +819,31 @@ def length_attn_weight_shapes(a: LengthAttn) -> dict[str, tuple]:
     """Keras variable shapes of one TransformerEncoder: the leaf names and shapes of a CrossFrameAttention layer with its
     feed-forward half (the two classes hold the same sub-layers under the same names, layers.py:2224-2245, :2321-2345)."""
     return frame_attn_weight_shapes(FrameAttn(a.name, a.channels, a.heads, a.key_dim, a.ff_dim, True))
+
+
+def hyena_weight_shapes(a: Hyena) -> dict[str, tuple]:
+    """Keras variable shapes of one HyenaBlock: the LayerNormalization's gamma / beta (C); the operator's ``order + 1``
+    bias-free projections (C, C); per order the filter network's Dense layers (16 -> filter_hidden ... -> C, the last one
+    alone with ``filter_layers`` 1) and the window's ``alphas`` / ``biases`` (order, C); the output projection if there is
+    one.  ``<name>/hyena/filter/pos_encoding`` (seq_len, 16) is optional and not listed: when the weights hold it the
+    filter table uses its rows (program.py: hyena_filter_tables)."""
+    c, n = a.channels, a.name
+    out: dict[str, tuple] = {f"{n}/norm/gamma": (c,), f"{n}/norm/beta": (c,)}
+    for k in range(a.order + 1):
+        out[f"{n}/hyena/proj_{k}/kernel"] = (c, c)
+    for o in range(a.order):
+        cin = HYENA_PE_DIM
+        for j in range(a.filter_layers):
+            units = c if j == a.filter_layers - 1 else a.filter_hidden
+            out[f"{n}/hyena/filter/ffn_{o}/dense_{j}/kernel"] = (cin, units)
+            out[f"{n}/hyena/filter/ffn_{o}/dense_{j}/bias"] = (units,)
+            cin = units
+    out[f"{n}/hyena/filter/alphas"] = (a.order, c)
+    out[f"{n}/hyena/filter/biases"] = (a.order, c)
+    if a.output_projection:
+        out[f"{n}/out_proj/kernel"] = (c, c)
+        out[f"{n}/out_proj/bias"] = (c,)
+    return out
 
 
 def frame_attn_flops_per_position(plan: ModelPlan) -> list[tuple[str, int, int]]:

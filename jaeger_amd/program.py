@@ -18,6 +18,8 @@ conv launches with epilogue stages:
 * ``axial_attention -> norm -> activation``                   per block a length-attention op (masked in block 0 only), a
   frame-attention op and an element-wise op with the post norm and the add of the block's input
   (``layers.py:2400-2517``); the mask kept; the norm / activation ride the last block's element-wise op
+* ``hyena_block -> norm -> activation``                       one hyena op (``layers.py:2724-3153``), out of place, the mask
+  kept; its implicit filters are tabled here once (:func:`hyena_filter_tables`) and travel in the weight blob
 
 Pure host logic (numpy + ctypes structs): unit-tested on CPU.
 """
@@ -29,7 +31,7 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 from . import _lib as L
-from .plan import Act, AxialAttn, Conv, Dense, FrameAttn, LengthAttn, LocalAttn, ModelPlan, Nmd, Norm, ResBlock, UnsupportedLayer, weight_shapes
+from .plan import HYENA_PE_DIM, Act, AxialAttn, Conv, Dense, FrameAttn, Hyena, LengthAttn, LocalAttn, ModelPlan, Nmd, Norm, ResBlock, UnsupportedLayer, weight_shapes
 
 _ACT_CODE = {None: L.ACT_NONE, "linear": L.ACT_NONE, "gelu": L.ACT_GELU_TANH, "gelu_erf": L.ACT_GELU_ERF,
              "relu": L.ACT_RELU, "tanh": L.ACT_TANH, "sigmoid": L.ACT_SIGMOID}
@@ -146,6 +148,96 @@ def pack_length_attn(a: LengthAttn, w: dict[str, np.ndarray]) -> np.ndarray:
     return pack_frame_attn(FrameAttn(a.name, a.channels, a.heads, a.key_dim, a.ff_dim, True), w)
 
 
+HYENA_EPSILON = 1e-6           # the LayerNormalization of a HyenaBlock (layers.py:3075)
+
+
+def hyena_position_rows(n_pos: int) -> np.ndarray:
+    """HyenaFilter._make_positional_encoding (layers.py:2871-2880) for positions 0 .. n_pos - 1 at pe_dim 16: the ARGUMENTS
+    ``pos * div`` as the reference forms them, float32 products of float32 factors (``div = exp(range(0, 16, 2) * -(log(10000)
+    / 16))``), their sine and cosine in float64; row ``[sin_0, cos_0, sin_1, cos_1, ...]``."""
+    f = np.float32
+    pos = np.arange(n_pos, dtype=f)[:, None]
+    div = np.exp(np.arange(0, HYENA_PE_DIM, 2, dtype=f) * f(-(np.log(f(10000.0)) / f(HYENA_PE_DIM)))).astype(f)
+    arg = (pos * div[None, :]).astype(f).astype(np.float64)
+    return np.stack([np.sin(arg), np.cos(arg)], axis=-1).reshape(n_pos, HYENA_PE_DIM)
+
+
+def _hyena_activation(name, x: np.ndarray) -> np.ndarray:
+    """HyenaFilter._hidden_activation (layers.py:2864-2869) in float64: "sin" is tf.sin, the others what Keras 3 resolves
+    the name to ("gelu": the tanh form)."""
+    if name is None or name == "linear":
+        return x
+    if name == "sin":
+        return np.sin(x)
+    if name == "gelu":
+        return 0.5 * x * (1.0 + np.tanh(np.sqrt(2.0 / np.pi) * (x + 0.044715 * x ** 3)))
+    if name == "relu":
+        return np.maximum(x, 0.0)
+    if name == "tanh":
+        return np.tanh(x)
+    if name == "sigmoid":
+        return 1.0 / (1.0 + np.exp(-x))
+    if name in ("silu", "swish"):
+        return x / (1.0 + np.exp(-x))
+    raise UnsupportedLayer(f"hyena filter_activation {name!r} cannot be evaluated on the host")
+
+
+def hyena_table_rows(a: Hyena) -> int:
+    """Rows of the layer's filter table: ``seq_len`` where the layer fixes it (the reference's stored positional encoding has
+    that many rows, a longer call fails there), else the position rows a program carries."""
+    return a.seq_len if a.seq_len is not None else POSITION_ROWS
+
+
+def hyena_filter_tables(a: Hyena, w: dict[str, np.ndarray], rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+    """HyenaFilter.call (layers.py:2882-2915) for every position the program may meet, once:
+    ``h[i, t, :] = (exp(-|alpha_i| t) + bias_i) * FFN_i(PE[t])`` as float32 ``(order, rows, C)``, evaluated in float64 from the
+    positional rows (the stored ``<name>/hyena/filter/pos_encoding`` of a layer with ``seq_len`` if the weights hold it, else recomputed) - and the
+    running sum of its squares over ``t``, ``ssq[i, t, :] = sum over s <= t of h[i, s, :] ** 2`` (of the float32 table, summed
+    in float64): with ``filter_normalize`` a call at ``l`` positions divides channel ``c`` of filter ``i`` by
+    ``sqrt(ssq[i, l - 1, c])``, and by nothing where that is zero (divide_no_nan)."""
+    rows = hyena_table_rows(a) if rows is None else rows
+    # (without seq_len the reference stores one row and recomputes the encoding at every call, :2817, :2888-2891)
+    stored = w.get(f"{a.name}/hyena/filter/pos_encoding") if a.seq_len is not None else None
+    if stored is not None:
+        stored = np.asarray(stored, np.float64)
+        if stored.ndim != 2 or stored.shape[1] != HYENA_PE_DIM or stored.shape[0] < rows:
+            raise ValueError(f"weight {a.name}/hyena/filter/pos_encoding: shape {stored.shape} != expected ({rows}, {HYENA_PE_DIM})")
+        pe = stored[:rows]
+    else:
+        pe = hyena_position_rows(rows)
+    f64 = lambda name: np.asarray(w[f"{a.name}/hyena/filter/{name}"], np.float64)
+    alphas, biases = np.abs(f64("alphas")), f64("biases")
+    t = np.arange(rows, dtype=np.float64)[:, None]
+    h = np.empty((a.order, rows, a.channels), np.float32)
+    for i in range(a.order):
+        x = pe
+        for j in range(a.filter_layers):
+            x = x @ f64(f"ffn_{i}/dense_{j}/kernel") + f64(f"ffn_{i}/dense_{j}/bias")
+            if j < a.filter_layers - 1:
+                x = _hyena_activation(a.filter_activation, x)
+        h[i] = ((np.exp(-alphas[i][None, :] * t) + biases[i][None, :]) * x).astype(np.float32)
+    ssq = np.cumsum(h.astype(np.float64) ** 2, axis=1).astype(np.float32)
+    return h, ssq
+
+
+def pack_hyena(a: Hyena, w: dict[str, np.ndarray]) -> np.ndarray:
+    """The weights and tables of one HyenaBlock as the kernels read them (csrc/jg_hyena.hip), folded in float64:
+    ``(n(x) * gamma + beta) @ W_k`` is ``n(x) @ (gamma[:, None] * W_k) + beta @ W_k`` - the kernel normalises only, and
+    zeroes the projections of a masked position.  Layout: wp [order + 1][C][C] | bp [order + 1][C] | with
+    output_projection wo [C][C] | bo [C] | h [order][rows][C] | with filter_normalize ssq [order][rows][C]."""
+    f64 = lambda name: np.asarray(w[f"{a.name}/{name}"], np.float64)
+    gamma, beta = f64("norm/gamma"), f64("norm/beta")
+    kernels = [f64(f"hyena/proj_{k}/kernel") for k in range(a.order + 1)]
+    out = [np.stack([gamma[:, None] * k for k in kernels]), np.stack([beta @ k for k in kernels])]
+    if a.output_projection:
+        out += [f64("out_proj/kernel"), f64("out_proj/bias")]
+    h, ssq = hyena_filter_tables(a, w)
+    out.append(h)
+    if a.filter_normalize:
+        out.append(ssq)
+    return np.concatenate([np.asarray(x, np.float32).ravel() for x in out])
+
+
 @dataclass
 class Program:
     ops: list            # list[L.JgOp]
@@ -173,13 +265,19 @@ class Program:
                         f"k={op.k} c={op.cin}->{op.cout} s={op.stride} d={op.dilation} [{st}]"
                         + (f" heads={op.k} ff={op.arg}" if op.kind == L.OP_FRAMEATTN else "")
                         + (f" heads={op.k} ff={op.arg} half_window={op.stride}" if op.kind == L.OP_LOCALATTN else "")
-                        + (f" heads={op.k} ff={op.arg}" if op.kind == L.OP_LENGTHATTN else ""))
+                        + (f" heads={op.k} ff={op.arg}" if op.kind == L.OP_LENGTHATTN else "")
+                        + (f" order={op.k} flags={op.arg} table_rows={op.stride}" if op.kind == L.OP_HYENA else ""))
         return rows
 
 
 class _Compiler:
     def __init__(self, plan: ModelPlan, weights: dict[str, np.ndarray]):
         self.plan, self.w = plan, weights
+        for layer in plan.rep:                  # (optional: the stored positional encoding of a layer with seq_len is used when it is there)
+            pe = f"{layer.name}/hyena/filter/pos_encoding" if isinstance(layer, Hyena) else None
+            if pe in weights and layer.seq_len is not None and tuple(weights[pe].shape) != (layer.seq_len, HYENA_PE_DIM):
+                raise ValueError(f"weight {pe}: shape {tuple(weights[pe].shape)} != expected ({layer.seq_len}, {HYENA_PE_DIM}) "
+                                 "(HyenaFilter stores the rows of its seq_len only)")
         missing = [n for n in weight_shapes(plan) if n not in weights]
         if missing:
             raise KeyError(f"weights missing for: {missing[:6]}{'...' if len(missing) > 6 else ''}")
@@ -538,6 +636,37 @@ class _Compiler:
                     buf = out
                 self._emit_ln_tail(layer.name, tail, mask, buf, layer.channels)
                 mask = mask2
+            elif isinstance(layer, Hyena):
+                # HyenaBlock multiplies by the mask on entry, behind its layer norm and on exit (layers.py:3109-3132): it
+                # reads valid positions only and writes Keras' exact values everywhere - zeros at masked positions.  So it
+                # may stand behind a local_attention with live dead positions, and its output holds none.  It keeps the mask
+                # (supports_masking, :3072).  The bias / batch norm / unmasked DyT / activation that follow ride the op's
+                # store; a LayerNorm or a masked DyT is cut off into an element-wise op behind it
+                if mask == L.JG_BUF_NONE:
+                    self._refuse_unmasked_reader(f"{layer.name}: hyena_block without a mask")
+                self.dead_margin = None
+                stages = []
+                i, mask2 = self._fuse_tail(layers, i + 1, stages, mask, layer.channels, pending)
+                if pending:
+                    raise UnsupportedLayer(f"{layer.name}: an nmd tap directly behind hyena_block is not supported "
+                                           "(the op's store carries no partial sums)")
+                tail = []
+                for j, st in enumerate(stages):
+                    if st.kind == L.ST_LN or (st.kind == L.ST_DYT and st.arg == 1):
+                        stages, tail = stages[:j], stages[j:]
+                        break
+                out = self.bufs.take()
+                op = self._op(L.OP_HYENA, in_buf=buf, out_buf=out, in_mask=mask, out_mask=mask, k=layer.order,
+                              cin=layer.channels, cout=layer.channels, stride=hyena_table_rows(layer), f0=HYENA_EPSILON,
+                              arg=(L.HYENA_OUT_PROJ if layer.output_projection else 0) | (L.HYENA_NORMALIZE if layer.filter_normalize else 0),
+                              w_off=self.blob.add(pack_hyena(layer, self.w)))
+                op.n_stages = len(stages)
+                for q, st in enumerate(stages):
+                    op.stages[q] = st
+                self.ops.append(op)
+                self._emit_ln_tail(layer.name, tail, mask, out, layer.channels)
+                self.bufs.give(buf)
+                buf, mask = out, mask2
             elif isinstance(layer, LengthAttn):
                 if buf == L.JG_BUF_IDS:
                     raise UnsupportedLayer(f"{layer.name}: transformer_encoder directly on the embedding is not supported")

@@ -58,7 +58,7 @@ def refuse_attention(plan: ModelPlan | None) -> None:
     names = attention_layers(plan) if plan is not None else []
     if names:
         raise UnsupportedLayer(f"verify-model does not cover {attention_kinds(plan)} layers ({', '.join(names)}): the graph census "
-                               "has no expectations for MultiHeadAttention / LayerNormalization nodes, and the SavedModel-bundle "
+                               "has no expectations for MultiHeadAttention / LayerNormalization / FFT nodes, and the SavedModel-bundle "
                                "loader does not map their variables - load such a model from <name>.weights.npz "
                                "(README: 'Attention models'; with a SavedModel directory beside it: --trust-project / "
                                "JAEGER_TRUST_PROJECT=1)")

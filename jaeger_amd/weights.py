@@ -12,11 +12,12 @@ var~U[0.5,1.5], seed 38341).  ``load_weights`` reads a model directory entry as 
 from __future__ import annotations
 
 import math
+import re
 from pathlib import Path
 
 import numpy as np
 
-from .plan import AxialAttn, Conv, Dense, FrameAttn, LengthAttn, LocalAttn, ModelPlan, Nmd, Norm, ResBlock, weight_shapes
+from .plan import AxialAttn, Conv, Dense, FrameAttn, Hyena, LengthAttn, LocalAttn, ModelPlan, Nmd, Norm, ResBlock, weight_shapes
 
 
 def random_weights(plan: ModelPlan, seed: int = 38341) -> dict[str, np.ndarray]:
@@ -36,6 +37,17 @@ def random_weights(plan: ModelPlan, seed: int = 38341) -> dict[str, np.ndarray]:
         else:  # bias, beta, moving_mean
             v = rng.normal(0.0, 0.1, shp)
         out[name] = v.astype(np.float32)
+    # a hyena filter's last Dense at 1/16: its positional rows change slowly, so a He-scaled FFN gives a filter whose lags
+    # add up coherently, every convolution multiplies the values by up to the row length, and the logits leave the range in
+    # which float32 resolves the 1e-4 the outputs are held to
+    last = {}
+    for name in out:
+        m = re.match(r"(.*/hyena/filter/ffn_\d+)/dense_(\d+)/", name)
+        if m:
+            last[m.group(1)] = max(last.get(m.group(1), 0), int(m.group(2)))
+    for ffn, j in last.items():
+        for leaf in ("kernel", "bias"):
+            out[f"{ffn}/dense_{j}/{leaf}"] *= np.float32(0.0625)
     return out
 
 
@@ -49,16 +61,18 @@ def load_npz(path) -> dict[str, np.ndarray]:
 
 
 def attention_layers(plan: ModelPlan) -> list[str]:
-    """Names of the plan's cross_frame_attention, local_attention, transformer_encoder and axial_attention layers."""
+    """Names of the plan's cross_frame_attention, local_attention, transformer_encoder, axial_attention and hyena_block
+    layers: the ones with nested sub-layers, whose weights load from ``.npz`` only."""
     return [l.name for seq in (plan.rep, plan.classifier, plan.reliability or []) for l in seq
-            if isinstance(l, (FrameAttn, LocalAttn, LengthAttn, AxialAttn))]
+            if isinstance(l, (FrameAttn, LocalAttn, LengthAttn, AxialAttn, Hyena))]
 
 
 def attention_kinds(plan: ModelPlan) -> str:
-    """The YAML names of the attention layer kinds the plan holds, for the refusals that name them."""
+    """The YAML names of the attention / hyena layer kinds the plan holds, for the refusals that name them."""
     layers = [l for seq in (plan.rep, plan.classifier, plan.reliability or []) for l in seq]
     kinds = [name for cls, name in ((FrameAttn, "cross_frame_attention"), (LocalAttn, "local_attention"),
-                                          (LengthAttn, "transformer_encoder"), (AxialAttn, "axial_attention"))
+                                          (LengthAttn, "transformer_encoder"), (AxialAttn, "axial_attention"),
+                                          (Hyena, "hyena_block"))
              if any(isinstance(l, cls) for l in layers)]
     return " / ".join(kinds)
 
@@ -69,13 +83,14 @@ NPZ_ROUTE = ("export the model's variables under their canonical names (README: 
 
 def _refuse_attention(plan: ModelPlan, what: str, source) -> None:
     """The Keras-3 ``.weights.h5`` and SavedModel-bundle loaders map weight groups onto plan layers by order and shapes.
-    A MultiHeadAttention nests four EinsumDense sub-layers whose key scheme in either container could only be guessed
-    here (no checkpoint of such a model and no Keras to write one): a guessed scheme would be untestable, so both
-    loaders refuse such a plan and name the route that works."""
+    A MultiHeadAttention nests four EinsumDense sub-layers - and a HyenaBlock an operator, a filter generator and its
+    Sequential filter networks - whose key scheme in either container could only be guessed here (no checkpoint of such
+    a model and no Keras to write one): a guessed scheme would be untestable, so both loaders refuse such a plan and name
+    the route that works."""
     names = attention_layers(plan)
     if names:
         raise AttentionWeightsUnsupported(
-            f"{source}: the {what} loader does not map the nested MultiHeadAttention variables of "
+            f"{source}: the {what} loader does not map the nested sub-layer variables (MultiHeadAttention, HyenaOperator) of "
             f"{attention_kinds(plan)} layers ({', '.join(names)}); {NPZ_ROUTE}")
 
 
