@@ -44,10 +44,8 @@ enum Place {
   PL_CONV_F16,     // split-f16 conv
   PL_CONV_F32,     // exact-f32 conv
   PL_POOL_FUSED,   // POOL finished from the partials its split-f16 conv left
-  PL_LOCALATTN,    // local attention: jg_localattn.hip (f32 rows, out of place, the mask kept)
+  PL_MIXER,        // a row mixer (below): launch_mixer
   PL_ORDINARY,     // the op's own kernel
-  PL_LENGTHATTN,   // full-row length attention: jg_lengthattn.hip (f32 rows, out of place)
-  PL_HYENA,        // hyena block: jg_hyena.hip (f32 rows, out of place, 2 + order launches through the projection scratch)
 };
 struct PlaceCtx {  // what placement depends on besides the model
   int prec;        // 0 exact f32, 1 split-f16
@@ -60,6 +58,45 @@ PlaceCtx jg_place_ctx(const jg_model *m, const std::vector<OpShape> *shp, int l)
 static inline PlaceCtx jg_place_nominal() { return PlaceCtx{1, true, false, false}; }
 Place jg_place_op(const jg_model *m, size_t i, const PlaceCtx &c);
 static inline bool jg_place_is_f16(Place p) { return p == PL_RB_CONV1 || p == PL_RB32 || p == PL_RB64 || p == PL_CONV_F16; }
+
+// ---- row mixers ------------------------------------------------------------------------------------------------------
+// The ops that read f32 rows (frames, L, C) from one activation slot and write rows of the same shape to another: packed
+// weights at w_off, an optional mask, bias / batch norm / unmasked DyT / activation stages fused into the store.  What
+// differs between them is the record below, the per-question switches of jg_model.hip (jg_mixer_*) and the kind-specific
+// lines of launch_mixer (jg_run.hip).
+enum MixerMask {
+  MM_NONE,          // out_mask = none
+  MM_KEEP,          // out_mask = in_mask (a mask slot or none)
+  MM_KEEP_OR_DROP,  // out_mask = in_mask or none
+};
+struct MixerKind {
+  int kind;
+  const char *noun;     // in messages
+  MixerMask mask;
+  bool six_frames;      // mixes across the six frames of a translated window (else: along each of the id_frames rows)
+  bool dilation_1;      // op.dilation must be 1
+  bool in_place;        // out_buf may be in_buf
+  int prof, prof_cvt;   // JG_PROF_* class of the launch and of a layout conversion in front of it (-1: not timed)
+};
+static const MixerKind jg_mixer_kinds[] = {
+    {JG_OP_FRAMEATTN, "frame attention", MM_NONE, true, false, true, JG_PROF_FRAMEATTN, JG_PROF_FRAMEATTN_CVT},
+    {JG_OP_LOCALATTN, "local attention", MM_KEEP, false, true, false, JG_PROF_LOCALATTN, JG_PROF_LOCALATTN_CVT},
+    {JG_OP_LENGTHATTN, "length attention", MM_KEEP_OR_DROP, false, false, false, -1, -1},
+    {JG_OP_HYENA, "hyena", MM_KEEP, false, true, false, -1, -1},
+};
+static inline const MixerKind *jg_mixer_kind(int kind) {      // nullptr: not a row mixer
+  for (const MixerKind &k : jg_mixer_kinds)
+    if (k.kind == kind) return &k;
+  return nullptr;
+}
+static inline bool jg_op_is_mixer(int kind) { return jg_mixer_kind(kind) != nullptr; }
+// FLOPs of op (a row mixer) over nw windows of the rows r records (jg_model.hip): the model's FLOPs and the profiling bracket
+double jg_mixer_flops(const jg_op &op, const OpShape &r, int nw);
+
+// does op read / write activation slot `buf` as a tensor (jg_prepare.hip; NMD_FINAL counts as a reader: it takes the
+// slot's shape)
+bool jg_op_reads(const jg_op &op, int buf);
+bool jg_op_writes(const jg_op &op, int buf);
 
 // ---- the rest ----------------------------------------------------------------------------------------------------------
 int jg_prepare_tab(jg_model *m, const float *weights);          // jg_prepare.hip, in the order jg_model_create calls them

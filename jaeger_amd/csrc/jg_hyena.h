@@ -27,6 +27,4 @@ bool jg_hyena_supports(int C, int order, int table_rows, char *why, size_t cap);
 int64_t jg_hyena_blob_floats(int C, int order, int table_rows, int flags);
 // floats of scratch one row of L positions needs
 int64_t jg_hyena_row_scratch(int C, int order, int L);
-// FLOPs of one row of L positions: the projections and 2 x order x C x L (L + 1) / 2 of the convolutions
-double jg_hyena_row_flops(int C, int order, int flags, int L);
 int jg_launch_hyena(jg_engine *e, const JgHyenaArgs &a, hipStream_t s);

@@ -304,11 +304,6 @@ int64_t jg_hyena_blob_floats(int C, int order, int table_rows, int flags) {
 
 int64_t jg_hyena_row_scratch(int C, int order, int L) { return (int64_t)(order + 1) * L * C; }
 
-double jg_hyena_row_flops(int C, int order, int flags, int L) {
-  const double dense = 2.0 * (order + 1 + ((flags & JG_HYENA_OUT_PROJ) ? 1 : 0)) * C * C * (double)L;
-  return dense + 2.0 * order * C * ((double)L * (L + 1) / 2);
-}
-
 int jg_launch_hyena(jg_engine *e, const JgHyenaArgs &a, hipStream_t s) {
   (void)e;
   char why[160];

@@ -21,6 +21,4 @@ struct JgLengthAttnArgs {
 bool jg_lengthattn_supports(int C, int H, int F, char *why, size_t cap);
 int64_t jg_lengthattn_blob_floats(int C, int F);
 int64_t jg_lengthattn_lds_bytes(int C, int H);
-// matrix-product FLOPs of one row of L positions: the dense products (k and v once per query tile) and 4 L^2 C of scores and context
-double jg_lengthattn_row_flops(int C, int F, int L);
 int jg_launch_lengthattn(jg_engine *e, const JgLengthAttnArgs &a, hipStream_t s);

@@ -400,11 +400,6 @@ int64_t jg_lengthattn_lds_bytes(int C, int H) {
   return ((int64_t)(2 * T + CH) * (C + 2) + (int64_t)CH * 2 * C + (int64_t)T * 2 * H + CH + T) * (int64_t)sizeof(float);
 }
 
-double jg_lengthattn_row_flops(int C, int F, int L) {
-  const double tiles = (L + T - 1) / T;
-  return 2.0 * (2.0 * C * C + 2.0 * C * F) * L + 2.0 * (2.0 * C * C) * L * tiles + 4.0 * (double)L * L * C;
-}
-
 int jg_launch_lengthattn(jg_engine *e, const JgLengthAttnArgs &a, hipStream_t s) {
   (void)e;
   char why[160];

@@ -19,7 +19,121 @@ static void conv_geometry(int L_in, int k, int stride, int dil, int padding, int
   }
 }
 
+// ---- row mixers: the questions with kind-specific arithmetic, one switch each (the rest is jg_mixer_kinds) ------------
+// op fields: cin = cout = channels, f0 = the layer norms' epsilon, w_off = the packed weights; the attention ops: k = heads,
+// arg = feed-forward width (frame attention: 0 = no feed-forward half), local attention: stride = half-window; hyena:
+// k = order, arg = flags, stride = rows of the filter table
+static bool mixer_supports(const jg_op &op, char *why, size_t cap) {      // sizes the kernel covers (why: the reason when not)
+  switch (op.kind) {
+    case JG_OP_FRAMEATTN: return jg_frameattn_supports(op.cin, op.k, op.arg, why, cap);
+    case JG_OP_LOCALATTN: return jg_localattn_supports(op.cin, op.k, op.arg, op.stride, why, cap);
+    case JG_OP_LENGTHATTN: return jg_lengthattn_supports(op.cin, op.k, op.arg, why, cap);
+    default: return jg_hyena_supports(op.cin, op.k, op.stride, why, cap);
+  }
+}
+
+static int64_t mixer_blob_floats(const jg_op &op) {
+  switch (op.kind) {
+    case JG_OP_FRAMEATTN: return jg_frameattn_blob_floats(op.cin, op.arg);
+    case JG_OP_LOCALATTN: return jg_localattn_blob_floats(op.cin, op.arg);
+    case JG_OP_LENGTHATTN: return jg_lengthattn_blob_floats(op.cin, op.arg);
+    default: return jg_hyena_blob_floats(op.cin, op.k, op.stride, op.arg);
+  }
+}
+
+static int64_t mixer_lds_bytes(const jg_op &op) {      // where the size depends on the op (0: a fixed size that always fits)
+  switch (op.kind) {
+    case JG_OP_LOCALATTN: return jg_localattn_lds_bytes(op.cin, op.cin / op.k, op.stride);
+    case JG_OP_LENGTHATTN: return jg_lengthattn_lds_bytes(op.cin, op.k);
+    default: return 0;
+  }
+}
+
+static int64_t mixer_row_scratch(const jg_op &op, int L) {      // floats of scratch one row of L positions needs
+  return op.kind == JG_OP_HYENA ? jg_hyena_row_scratch(op.cin, op.k, L) : 0;
+}
+
+double jg_mixer_flops(const jg_op &op, const OpShape &r, int nw) {
+  const int C = op.cin, L = r.in.L;
+  const double rows = (double)(nw * r.in.frames);
+  switch (op.kind) {
+    case JG_OP_FRAMEATTN:      // the four dense products
+      return 2.0 * (4.0 * C * C + 2.0 * C * op.arg) * rows * L;
+    case JG_OP_LOCALATTN: {
+      // q, the projection and the feed-forward half per position; k and v per position and per halo position of its tile
+      const int hb = (op.stride + 15) / 16;
+      const double kv_share = (double)(JG_LOCALATTN_TILE + 32 * hb) / JG_LOCALATTN_TILE;
+      return 2.0 * ((2.0 + 2.0 * kv_share) * C * C + 2.0 * C * op.arg) * rows * L;
+    }
+    case JG_OP_LENGTHATTN: {   // dense products (k and v once per query tile) plus 4 L^2 C of scores and context
+      const double tiles = (L + JG_LENGTHATTN_TILE - 1) / JG_LENGTHATTN_TILE;
+      return (2.0 * (2.0 * C * C + 2.0 * C * op.arg) * L + 2.0 * (2.0 * C * C) * L * tiles + 4.0 * (double)L * L * C) * rows;
+    }
+    default: {                 // hyena: the projections and 2 x order x C x L (L + 1) / 2 of the convolutions
+      const double dense = 2.0 * (op.k + 1 + ((op.arg & JG_HYENA_OUT_PROJ) ? 1 : 0)) * C * C * (double)L;
+      return (dense + 2.0 * op.k * C * ((double)L * (L + 1) / 2)) * rows;
+    }
+  }
+}
+
+static int mixer_describe(const jg_op &op, size_t i, char *line, size_t cap) {      // without the conversion note and the newline
+  switch (op.kind) {
+    case JG_OP_FRAMEATTN:
+      return snprintf(line, cap, "op %zu: frame attention c=%d heads=%d key_dim=%d ff=%d -> one launch, exact-f32 matrix cores, f32 rows",
+                      i, op.cin, op.k, op.cin / op.k, op.arg);
+    case JG_OP_LOCALATTN:
+      return snprintf(line, cap, "op %zu: local attention c=%d heads=%d key_dim=%d ff=%d half_window=%d %s -> one launch, exact-f32 matrix cores, f32 rows",
+                      i, op.cin, op.k, op.cin / op.k, op.arg, op.stride, op.in_mask >= 0 ? "masked keys" : "no mask");
+    case JG_OP_LENGTHATTN:
+      return snprintf(line, cap, "op %zu: length attention c=%d heads=%d key_dim=%d ff=%d %s -> one launch, exact-f32 matrix cores (dense), vector ALUs (scores, context), f32 rows",
+                      i, op.cin, op.k, op.cin / op.k, op.arg, op.in_mask >= 0 ? "masked queries and keys" : "no mask");
+    default:
+      return snprintf(line, cap, "op %zu: hyena c=%d order=%d table_rows=%d%s%s %s -> %d launches: projections on the exact-f32 matrix cores, causal convolutions on the vector ALUs, f32 rows",
+                      i, op.cin, op.k, op.stride, (op.arg & JG_HYENA_OUT_PROJ) ? " output_projection" : "", (op.arg & JG_HYENA_NORMALIZE) ? " filter_normalize" : "",
+                      op.in_mask >= 0 ? "masked" : "no mask", 2 + op.k);
+  }
+}
+
+static int validate_mixer(const jg_model *m, size_t i) {
+  const jg_op &op = m->ops[i];
+  const MixerKind &mk = *jg_mixer_kind(op.kind);
+  JG_REQUIRE(op.in_buf >= 0 && op.out_buf >= 0 && op.cin == op.cout && op.f0 > 0.f && (!mk.dilation_1 || op.dilation == 1), JG_ERR_INVALID,
+             "op %zu: a %s op reads and writes an activation slot of cin = cout channels", i, mk.noun);
+  JG_REQUIRE(mk.in_place || op.in_buf != op.out_buf, JG_ERR_INVALID,
+             "op %zu: a %s op cannot run in place (its workgroups read rows that others write)", i, mk.noun);
+  const bool mask_slot = op.in_mask >= 0 || op.in_mask == JG_BUF_NONE;
+  switch (mk.mask) {
+    case MM_NONE:
+      JG_REQUIRE(op.out_mask == JG_BUF_NONE, JG_ERR_INVALID, "op %zu: a %s op leaves no mask (out_mask = none)", i, mk.noun);
+      break;
+    case MM_KEEP:
+      JG_REQUIRE(mask_slot && op.out_mask == op.in_mask, JG_ERR_INVALID,
+                 "op %zu: a %s op keeps its mask (out_mask = in_mask, a mask slot or none)", i, mk.noun);
+      break;
+    case MM_KEEP_OR_DROP:
+      JG_REQUIRE(mask_slot && (op.out_mask == op.in_mask || op.out_mask == JG_BUF_NONE), JG_ERR_INVALID,
+                 "op %zu: a %s op keeps its mask or drops it (out_mask = in_mask or none)", i, mk.noun);
+      break;
+  }
+  if (op.kind == JG_OP_HYENA)
+    JG_REQUIRE((op.arg & ~(JG_HYENA_OUT_PROJ | JG_HYENA_NORMALIZE)) == 0, JG_ERR_INVALID, "op %zu: hyena flags %d", i, op.arg);
+  char why[160];
+  JG_REQUIRE(mixer_supports(op, why, sizeof(why)), JG_ERR_UNSUPPORTED, "op %zu: %s with %s", i, mk.noun, why);
+  JG_REQUIRE(mixer_lds_bytes(op) <= 160 * 1024, JG_ERR_UNSUPPORTED, "op %zu: %s needs %lld bytes of LDS", i, mk.noun, (long long)mixer_lds_bytes(op));
+  JG_REQUIRE(m->ops.back().kind != JG_OP_STRANDS, JG_ERR_UNSUPPORTED,
+             "op %zu: %s needs the frame rows of a translated window (not a strand program)", i, mk.noun);
+  JG_REQUIRE(op.w_off >= 0 && op.w_off + mixer_blob_floats(op) <= m->n_w, JG_ERR_INVALID,
+             "op %zu: %s weights outside the weight blob", i, mk.noun);
+  for (int s = 0; s < op.n_stages; ++s) {
+    const int kd = op.stages[s].kind;
+    JG_REQUIRE(kd == JG_ST_BIAS || kd == JG_ST_BN || kd == JG_ST_ACT || (kd == JG_ST_DYT && op.stages[s].arg == 0), JG_ERR_UNSUPPORTED,
+               "op %zu stage %d: only bias / batch norm / unmasked DyT / activation stages fuse behind %s (kind %d)", i, s, mk.noun, kd);
+  }
+  return JG_OK;
+}
+
 static int validate_program(const jg_model *m) {
+  int rc;
   for (size_t i = 0; i < m->ops.size(); ++i) {
     const jg_op &op = m->ops[i];
     auto slot_ok = [](int s, bool allow_ids) {
@@ -63,89 +177,7 @@ static int validate_program(const jg_model *m) {
       JG_REQUIRE(op.in_buf != JG_BUF_IDS && op.in_mask != JG_BUF_IDS, JG_ERR_INVALID,
                  "op %zu: reads the id tensor directly in a program that opens with an embedding op (its buffer and mask take the tensor's place)", i);
     }
-    if (op.kind == JG_OP_FRAMEATTN) {
-      // cin = cout = channels, k = heads, arg = feed-forward width (0: no feed-forward half), f0 = the layer norms' epsilon
-      JG_REQUIRE(op.in_buf >= 0 && op.out_buf >= 0 && op.cin == op.cout && op.out_mask == JG_BUF_NONE && op.f0 > 0.f,
-                 JG_ERR_INVALID, "op %zu: a frame-attention op reads and writes an activation slot of cin = cout channels and leaves no mask", i);
-      char why[160];
-      JG_REQUIRE(jg_frameattn_supports(op.cin, op.k, op.arg, why, sizeof(why)), JG_ERR_UNSUPPORTED,
-                 "op %zu: frame attention with %s", i, why);
-      JG_REQUIRE(m->ops.back().kind != JG_OP_STRANDS, JG_ERR_UNSUPPORTED,
-                 "op %zu: frame attention needs the six frames of a translated window (not a strand program)", i);
-      JG_REQUIRE(off_ok(op.w_off, jg_frameattn_blob_floats(op.cin, op.arg)), JG_ERR_INVALID,
-                 "op %zu: frame-attention weights outside the weight blob", i);
-      for (int s = 0; s < op.n_stages; ++s) {
-        const int kd = op.stages[s].kind;
-        JG_REQUIRE(kd == JG_ST_BIAS || kd == JG_ST_BN || kd == JG_ST_ACT || (kd == JG_ST_DYT && op.stages[s].arg == 0), JG_ERR_UNSUPPORTED,
-                   "op %zu stage %d: only bias / batch norm / unmasked DyT / activation stages fuse behind frame attention (kind %d)", i, s, kd);
-      }
-    }
-    if (op.kind == JG_OP_LOCALATTN) {
-      // cin = cout = channels, k = heads, arg = feed-forward width, stride = half-window, f0 = the layer norms' epsilon
-      JG_REQUIRE(op.in_buf >= 0 && op.out_buf >= 0 && op.cin == op.cout && op.f0 > 0.f && op.dilation == 1, JG_ERR_INVALID,
-                 "op %zu: a local-attention op reads and writes an activation slot of cin = cout channels", i);
-      JG_REQUIRE(op.in_buf != op.out_buf, JG_ERR_INVALID,
-                 "op %zu: a local-attention op cannot run in place (a tile reads its neighbours' positions as its halo)", i);
-      JG_REQUIRE((op.in_mask >= 0 || op.in_mask == JG_BUF_NONE) && op.out_mask == op.in_mask, JG_ERR_INVALID,
-                 "op %zu: a local-attention op keeps its mask (out_mask = in_mask, a mask slot or none)", i);
-      char why[160];
-      JG_REQUIRE(jg_localattn_supports(op.cin, op.k, op.arg, op.stride, why, sizeof(why)), JG_ERR_UNSUPPORTED,
-                 "op %zu: local attention with %s", i, why);
-      JG_REQUIRE(jg_localattn_lds_bytes(op.cin, op.cin / op.k, op.stride) <= 160 * 1024, JG_ERR_UNSUPPORTED,
-                 "op %zu: local attention needs %lld bytes of LDS", i, (long long)jg_localattn_lds_bytes(op.cin, op.cin / op.k, op.stride));
-      JG_REQUIRE(m->ops.back().kind != JG_OP_STRANDS, JG_ERR_UNSUPPORTED,
-                 "op %zu: local attention needs the frame rows of a translated window (not a strand program)", i);
-      JG_REQUIRE(off_ok(op.w_off, jg_localattn_blob_floats(op.cin, op.arg)), JG_ERR_INVALID,
-                 "op %zu: local-attention weights outside the weight blob", i);
-      for (int s = 0; s < op.n_stages; ++s) {
-        const int kd = op.stages[s].kind;
-        JG_REQUIRE(kd == JG_ST_BIAS || kd == JG_ST_BN || kd == JG_ST_ACT || (kd == JG_ST_DYT && op.stages[s].arg == 0), JG_ERR_UNSUPPORTED,
-                   "op %zu stage %d: only bias / batch norm / unmasked DyT / activation stages fuse behind local attention (kind %d)", i, s, kd);
-      }
-    }
-    if (op.kind == JG_OP_LENGTHATTN) {
-      // cin = cout = channels, k = heads, arg = feed-forward width, f0 = the layer norms' epsilon
-      JG_REQUIRE(op.in_buf >= 0 && op.out_buf >= 0 && op.cin == op.cout && op.f0 > 0.f, JG_ERR_INVALID,
-                 "op %zu: a length-attention op reads and writes an activation slot of cin = cout channels", i);
-      JG_REQUIRE(op.in_buf != op.out_buf, JG_ERR_INVALID,
-                 "op %zu: a length-attention op cannot run in place (every query tile reads the whole row)", i);
-      JG_REQUIRE((op.in_mask >= 0 || op.in_mask == JG_BUF_NONE) && (op.out_mask == op.in_mask || op.out_mask == JG_BUF_NONE), JG_ERR_INVALID,
-                 "op %zu: a length-attention op keeps its mask or drops it (out_mask = in_mask or none)", i);
-      char why[160];
-      JG_REQUIRE(jg_lengthattn_supports(op.cin, op.k, op.arg, why, sizeof(why)), JG_ERR_UNSUPPORTED,
-                 "op %zu: length attention with %s", i, why);
-      JG_REQUIRE(jg_lengthattn_lds_bytes(op.cin, op.k) <= 160 * 1024, JG_ERR_UNSUPPORTED,
-                 "op %zu: length attention needs %lld bytes of LDS", i, (long long)jg_lengthattn_lds_bytes(op.cin, op.k));
-      JG_REQUIRE(m->ops.back().kind != JG_OP_STRANDS, JG_ERR_UNSUPPORTED,
-                 "op %zu: length attention needs the frame rows of a translated window (not a strand program)", i);
-      JG_REQUIRE(off_ok(op.w_off, jg_lengthattn_blob_floats(op.cin, op.arg)), JG_ERR_INVALID,
-                 "op %zu: length-attention weights outside the weight blob", i);
-      for (int s = 0; s < op.n_stages; ++s) {
-        const int kd = op.stages[s].kind;
-        JG_REQUIRE(kd == JG_ST_BIAS || kd == JG_ST_BN || kd == JG_ST_ACT || (kd == JG_ST_DYT && op.stages[s].arg == 0), JG_ERR_UNSUPPORTED,
-                   "op %zu stage %d: only bias / batch norm / unmasked DyT / activation stages fuse behind length attention (kind %d)", i, s, kd);
-      }
-    }
-    if (op.kind == JG_OP_HYENA) {
-      // cin = cout = channels, k = order, arg = flags, stride = rows of the filter table, f0 = the layer norm's epsilon
-      JG_REQUIRE(op.in_buf >= 0 && op.out_buf >= 0 && op.cin == op.cout && op.f0 > 0.f && op.dilation == 1, JG_ERR_INVALID,
-                 "op %zu: a hyena op reads and writes an activation slot of cin = cout channels", i);
-      JG_REQUIRE(op.in_buf != op.out_buf, JG_ERR_INVALID, "op %zu: a hyena op cannot run in place", i);
-      JG_REQUIRE((op.in_mask >= 0 || op.in_mask == JG_BUF_NONE) && op.out_mask == op.in_mask, JG_ERR_INVALID,
-                 "op %zu: a hyena op keeps its mask (out_mask = in_mask, a mask slot or none)", i);
-      JG_REQUIRE((op.arg & ~(JG_HYENA_OUT_PROJ | JG_HYENA_NORMALIZE)) == 0, JG_ERR_INVALID, "op %zu: hyena flags %d", i, op.arg);
-      char why[160];
-      JG_REQUIRE(jg_hyena_supports(op.cin, op.k, op.stride, why, sizeof(why)), JG_ERR_UNSUPPORTED, "op %zu: hyena with %s", i, why);
-      JG_REQUIRE(m->ops.back().kind != JG_OP_STRANDS, JG_ERR_UNSUPPORTED,
-                 "op %zu: hyena needs the frame rows of a translated window (not a strand program)", i);
-      JG_REQUIRE(off_ok(op.w_off, jg_hyena_blob_floats(op.cin, op.k, op.stride, op.arg)), JG_ERR_INVALID,
-                 "op %zu: hyena weights and filter table outside the weight blob", i);
-      for (int s = 0; s < op.n_stages; ++s) {
-        const int kd = op.stages[s].kind;
-        JG_REQUIRE(kd == JG_ST_BIAS || kd == JG_ST_BN || kd == JG_ST_ACT || (kd == JG_ST_DYT && op.stages[s].arg == 0), JG_ERR_UNSUPPORTED,
-                   "op %zu stage %d: only bias / batch norm / unmasked DyT / activation stages fuse behind a hyena op (kind %d)", i, s, kd);
-      }
-    }
+    if (jg_op_is_mixer(op.kind) && (rc = validate_mixer(m, i)) != JG_OK) return rc;
     if (op.kind == JG_OP_DENSE) {
       JG_REQUIRE(off_ok(op.w_off, (int64_t)op.cin * op.cout), JG_ERR_INVALID,
                  "op %zu: dense kernel outside the weight blob", i);
@@ -234,42 +266,6 @@ int jg_shape_walk(const jg_model *m, int l, std::vector<OpShape> &shp) {
         JG_REQUIRE(r.in.C == op.cout, JG_ERR_INVALID, "op %zu: eltwise channel mismatch", i);
         r.out = r.in;
         break;
-      case JG_OP_FRAMEATTN:
-        JG_REQUIRE(r.in.C == op.cin && r.in.frames == 6, JG_ERR_INVALID,
-                   "op %zu: frame attention over %d channels expects (6, L, %d) rows, input is (%d, L, %d)", i, op.cin, op.cin, r.in.frames, r.in.C);
-        r.out = r.in;
-        break;
-      case JG_OP_LOCALATTN:
-        JG_REQUIRE(r.in.C == op.cin && r.in.frames == m->id_frames, JG_ERR_INVALID,
-                   "op %zu: local attention over %d channels expects (%d, L, %d) rows, input is (%d, L, %d)", i, op.cin, m->id_frames, op.cin, r.in.frames, r.in.C);
-        if (op.in_mask >= 0) {
-          r.m_in = mL[op.in_mask];
-          JG_REQUIRE(r.m_in == r.in.L, JG_ERR_INVALID, "op %zu: local attention over rows of %d positions with a mask of %d", i, r.in.L, r.m_in);
-        }
-        r.out = r.in;
-        break;
-      case JG_OP_LENGTHATTN:
-        JG_REQUIRE(r.in.C == op.cin && r.in.frames == m->id_frames, JG_ERR_INVALID,
-                   "op %zu: length attention over %d channels expects (%d, L, %d) rows, input is (%d, L, %d)", i, op.cin, m->id_frames, op.cin, r.in.frames, r.in.C);
-        if (op.in_mask >= 0) {
-          r.m_in = mL[op.in_mask];
-          JG_REQUIRE(r.m_in == r.in.L, JG_ERR_INVALID, "op %zu: length attention over rows of %d positions with a mask of %d", i, r.in.L, r.m_in);
-        }
-        r.out = r.in;
-        break;
-      case JG_OP_HYENA:
-        JG_REQUIRE(r.in.C == op.cin && r.in.frames == m->id_frames, JG_ERR_INVALID,
-                   "op %zu: hyena over %d channels expects (%d, L, %d) rows, input is (%d, L, %d)", i, op.cin, m->id_frames, op.cin, r.in.frames, r.in.C);
-        if (op.in_mask >= 0) {
-          r.m_in = mL[op.in_mask];
-          JG_REQUIRE(r.m_in == r.in.L, JG_ERR_INVALID, "op %zu: hyena over rows of %d positions with a mask of %d", i, r.in.L, r.m_in);
-        }
-        JG_REQUIRE(r.in.L <= op.stride, JG_ERR_UNSUPPORTED,
-                   "op %zu: hyena over rows of %d positions, the layer's filter table holds %d (seq_len of the layer, or the %d rows a program carries)",
-                   i, r.in.L, op.stride, op.stride);
-        r.scratch = (int64_t)r.in.frames * jg_hyena_row_scratch(op.cin, op.k, r.in.L);
-        r.out = r.in;
-        break;
       case JG_OP_MAXPOOL1D:
         r.L_out = r.in.L / 2;
         JG_REQUIRE(r.L_out > 0, JG_ERR_INVALID, "op %zu: maxpool output empty", i);
@@ -298,7 +294,23 @@ int jg_shape_walk(const jg_model *m, int l, std::vector<OpShape> &shp) {
                    op.k, op.cout, op.in_vec, vw[op.in_vec]);
         r.vec_need = op.vec_off + op.cout;
         break;
-      default: break;
+      default: {
+        if (!jg_op_is_mixer(op.kind)) break;
+        const MixerKind &mk = *jg_mixer_kind(op.kind);
+        const int frames = mk.six_frames ? 6 : m->id_frames;
+        JG_REQUIRE(r.in.C == op.cin && r.in.frames == frames, JG_ERR_INVALID,
+                   "op %zu: %s over %d channels expects (%d, L, %d) rows, input is (%d, L, %d)", i, mk.noun, op.cin, frames, op.cin, r.in.frames, r.in.C);
+        if (mk.mask != MM_NONE && op.in_mask >= 0) {
+          r.m_in = mL[op.in_mask];
+          JG_REQUIRE(r.m_in == r.in.L, JG_ERR_INVALID, "op %zu: %s over rows of %d positions with a mask of %d", i, mk.noun, r.in.L, r.m_in);
+        }
+        if (op.kind == JG_OP_HYENA)
+          JG_REQUIRE(r.in.L <= op.stride, JG_ERR_UNSUPPORTED,
+                     "op %zu: hyena over rows of %d positions, the layer's filter table holds %d (seq_len of the layer, or the %d rows a program carries)",
+                     i, r.in.L, op.stride, op.stride);
+        r.scratch = (int64_t)r.in.frames * mixer_row_scratch(op, r.in.L);
+        r.out = r.in;
+      } break;
     }
     if (r.out.frames > 0) sh[op.out_buf] = r.out;
     if (r.m_out > 0) mL[op.out_mask] = r.m_out;
@@ -318,24 +330,12 @@ static void fold_shapes(const jg_model *m, int l, const std::vector<OpShape> &sh
     const jg_op &op = m->ops[i];
     const OpShape &r = shp[i];
     if (op.kind == JG_OP_CONV) fl += 2.0 * op.k * op.cin * op.cout * (double)r.in.frames * r.L_out;
-    if (op.kind == JG_OP_FRAMEATTN)
-      fl += 2.0 * (4.0 * op.cin * op.cin + 2.0 * op.cin * op.arg) * (double)r.in.frames * r.in.L;   // the four dense products
-    if (op.kind == JG_OP_LOCALATTN) {
-      // q, the projection and the feed-forward half per position; k and v per position and per halo position of its tile
-      const int hb = (op.stride + 15) / 16;
-      const double kv_share = (double)(JG_LOCALATTN_TILE + 32 * hb) / JG_LOCALATTN_TILE;
-      fl += 2.0 * ((2.0 + 2.0 * kv_share) * op.cin * op.cin + 2.0 * op.cin * op.arg) * (double)r.in.frames * r.in.L;
-    }
-    if (op.kind == JG_OP_LENGTHATTN)      // dense products (k and v once per query tile) plus 4 L^2 C of scores and context
-      fl += jg_lengthattn_row_flops(op.cin, op.arg, r.in.L) * (double)r.in.frames;
-    if (op.kind == JG_OP_HYENA)           // the projections and 2 x order x C x L (L + 1) / 2 of the convolutions
-      fl += jg_hyena_row_flops(op.cin, op.k, op.arg, r.in.L) * (double)r.in.frames;
+    if (jg_op_is_mixer(op.kind)) fl += jg_mixer_flops(op, r, 1);
     if (r.m_out > 0) msk_elems[op.out_mask] = std::max<int64_t>(msk_elems[op.out_mask], (int64_t)m->id_frames * r.m_out);
     if (r.vec_need > 0) vec_w[op.out_vec] = std::max(vec_w[op.out_vec], r.vec_need);
     if (r.out.frames == 0 || (tab && (int)i == m->tab_conv)) continue;      // (table net: the activation never exists)
     // (+ one position for an odd row: a phase-split tensor holds two phases of (L + 1) / 2 positions)
-    const bool ps_room = op.kind == JG_OP_CONV || op.kind == JG_OP_EMBED || op.kind == JG_OP_FRAMEATTN || op.kind == JG_OP_LOCALATTN ||
-                         op.kind == JG_OP_LENGTHATTN || op.kind == JG_OP_HYENA;
+    const bool ps_room = op.kind == JG_OP_CONV || op.kind == JG_OP_EMBED || jg_op_is_mixer(op.kind);
     const Shape &t = r.out;
     act_elems[op.out_buf] = std::max<int64_t>(act_elems[op.out_buf], (int64_t)t.frames * (t.L + (ps_room ? t.L & 1 : 0)) * t.C);
     const int tiles = std::max((t.L + 63) / 64, 8 * ((t.L + 255) / 256));
@@ -370,33 +370,10 @@ extern "C" int jg_model_describe(const jg_model *m, char *buf, int64_t cap) {
   char line[512];
   for (size_t i = 0; i < m->ops.size(); ++i) {
     const jg_op &op = m->ops[i];
-    if (op.kind == JG_OP_FRAMEATTN) {
-      snprintf(line, sizeof(line), "op %zu: frame attention c=%d heads=%d key_dim=%d ff=%d -> one launch, exact-f32 matrix cores, f32 rows%s\n",
-               i, op.cin, op.k, op.cin / op.k, op.arg,
-               (m->f16_eligible && m->hprep[i].n_cvt > 0) ? " (F16S -> f32 conversion in front)" : "");
+    if (jg_op_is_mixer(op.kind)) {
+      mixer_describe(op, i, line, sizeof(line));
       out += line;
-      continue;
-    }
-    if (op.kind == JG_OP_LOCALATTN) {
-      snprintf(line, sizeof(line), "op %zu: local attention c=%d heads=%d key_dim=%d ff=%d half_window=%d %s -> one launch, exact-f32 matrix cores, f32 rows%s\n",
-               i, op.cin, op.k, op.cin / op.k, op.arg, op.stride, op.in_mask >= 0 ? "masked keys" : "no mask",
-               (m->f16_eligible && m->hprep[i].n_cvt > 0) ? " (F16S -> f32 conversion in front)" : "");
-      out += line;
-      continue;
-    }
-    if (op.kind == JG_OP_LENGTHATTN) {
-      snprintf(line, sizeof(line), "op %zu: length attention c=%d heads=%d key_dim=%d ff=%d %s -> one launch, exact-f32 matrix cores (dense), vector ALUs (scores, context), f32 rows%s\n",
-               i, op.cin, op.k, op.cin / op.k, op.arg, op.in_mask >= 0 ? "masked queries and keys" : "no mask",
-               (m->f16_eligible && m->hprep[i].n_cvt > 0) ? " (F16S -> f32 conversion in front)" : "");
-      out += line;
-      continue;
-    }
-    if (op.kind == JG_OP_HYENA) {
-      snprintf(line, sizeof(line), "op %zu: hyena c=%d order=%d table_rows=%d%s%s %s -> %d launches: projections on the exact-f32 matrix cores, causal convolutions on the vector ALUs, f32 rows%s\n",
-               i, op.cin, op.k, op.stride, (op.arg & JG_HYENA_OUT_PROJ) ? " output_projection" : "", (op.arg & JG_HYENA_NORMALIZE) ? " filter_normalize" : "",
-               op.in_mask >= 0 ? "masked" : "no mask", 2 + op.k,
-               (m->f16_eligible && m->hprep[i].n_cvt > 0) ? " (F16S -> f32 conversion in front)" : "");
-      out += line;
+      out += (m->f16_eligible && m->hprep[i].n_cvt > 0) ? " (F16S -> f32 conversion in front)\n" : "\n";
       continue;
     }
     if (op.kind != JG_OP_CONV) continue;
@@ -624,8 +601,7 @@ int jg_ensure_workspace(jg_model *m, int64_t chunk, int l, const std::vector<OpS
 const char *jg_tap_refusal(const jg_model *m, size_t i, const PlaceCtx &c, int l, char *why, size_t cap) {
   const jg_op &op = m->ops[i];
   if (op.kind != JG_OP_CONV && op.kind != JG_OP_MASK && op.kind != JG_OP_ELTWISE && op.kind != JG_OP_EMBED &&
-      op.kind != JG_OP_MAXPOOL1D && op.kind != JG_OP_FRAMESUM && op.kind != JG_OP_FRAMEATTN && op.kind != JG_OP_LOCALATTN &&
-      op.kind != JG_OP_LENGTHATTN && op.kind != JG_OP_HYENA) {
+      op.kind != JG_OP_MAXPOOL1D && op.kind != JG_OP_FRAMESUM && !jg_op_is_mixer(op.kind)) {
     snprintf(why, cap, "op %zu (kind %d) writes a vector or nothing - pool, dense and vector results are outputs already", i, op.kind);
     return why;
   }
@@ -681,7 +657,7 @@ int jg_tap_copy(jg_model *m, size_t i, const OpShape &r, const PlaceCtx &c, int 
   if (pl == PL_CONV_F16 && m->tap_flat) v |= JG_TAP_WINDOW_PACKED;
   if (f16_conv && hp.d_lut != nullptr) v |= JG_TAP_TABLE_LOOKUP;
   if (f16_conv && hp.cw != 128) v |= JG_TAP_NARROW;
-  if (op.kind == JG_OP_FRAMEATTN || op.kind == JG_OP_LOCALATTN || op.kind == JG_OP_LENGTHATTN || op.kind == JG_OP_HYENA) v |= JG_TAP_EXACT_F32;      // one arithmetic (exact-f32 matrix cores), one layout (f32 rows)
+  if (jg_op_is_mixer(op.kind)) v |= JG_TAP_EXACT_F32;      // one arithmetic (exact-f32 matrix cores), one layout (f32 rows)
   m->tap_variant |= v;
   float *out = reinterpret_cast<float *>(dst + m->tap_row0 * per_row);
   if (!f16s) {

@@ -63,7 +63,7 @@ int jg_prepare_small(jg_model *m, const float *weights) {
   for (size_t i = (size_t)pool_op + 1; i < m->ops.size(); ++i) {
     const int k = m->ops[i].kind;
     if (k == JG_OP_CONV || k == JG_OP_MASK || k == JG_OP_POOL || k == JG_OP_ELTWISE || k == JG_OP_MAXPOOL1D ||
-        k == JG_OP_FRAMESUM || k == JG_OP_NMD_FINAL || k == JG_OP_FRAMEATTN || k == JG_OP_LOCALATTN || k == JG_OP_LENGTHATTN || k == JG_OP_HYENA)
+        k == JG_OP_FRAMESUM || k == JG_OP_NMD_FINAL || jg_op_is_mixer(k))
       return JG_OK;
   }
   JgSmallNet *sn = new JgSmallNet();
@@ -327,6 +327,23 @@ int jg_prepare_f32(jg_model *m, const float *weights) {
     JG_HIP(hipMemcpy(m->hprep[i].d_w8, w8.data(), w8.size() * sizeof(float), hipMemcpyHostToDevice));
   }
   return JG_OK;
+}
+
+// Does op read / write activation slot `buf` as a tensor?  The format pass, the phase-split plan and the residual-block plan
+// all go by these two.
+bool jg_op_reads(const jg_op &o, int buf) {
+  if ((o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM || o.kind == JG_OP_POOL ||
+       o.kind == JG_OP_NMD_FINAL || jg_op_is_mixer(o.kind)) && o.in_buf == buf)
+    return true;
+  if (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE)
+    for (int q = 0; q < o.n_stages; ++q)
+      if (o.stages[q].kind == JG_ST_ADD && o.stages[q].arg == buf) return true;
+  return false;
+}
+
+bool jg_op_writes(const jg_op &o, int buf) {
+  return (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM || o.kind == JG_OP_EMBED ||
+          jg_op_is_mixer(o.kind)) && o.out_buf == buf;
 }
 
 int jg_prepare_f16(jg_model *m, const float *weights) {
@@ -605,22 +622,8 @@ int jg_prepare_f16(jg_model *m, const float *weights) {
       if (o.stages[q].kind == JG_ST_ADD && o.stages[q].arg == buf) return true;
     return false;
   };
-  auto reads = [&](size_t j, int buf) {
-    const jg_op &o = m->ops[j];
-    if ((o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-         o.kind == JG_OP_POOL || o.kind == JG_OP_NMD_FINAL || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN || o.kind == JG_OP_HYENA) && o.in_buf == buf)
-      return o.kind != JG_OP_NMD_FINAL;               // (NMD_FINAL only takes the slot's shape)
-    if (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE)
-      for (int q = 0; q < o.n_stages; ++q)
-        if (o.stages[q].kind == JG_ST_ADD && o.stages[q].arg == buf) return true;
-    return false;
-  };
-  auto writes = [&](size_t j, int buf) {
-    const jg_op &o = m->ops[j];
-    return (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-            o.kind == JG_OP_EMBED || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN || o.kind == JG_OP_HYENA) &&
-           o.out_buf == buf;
-  };
+  // (NMD_FINAL only takes the slot's shape: no format is asked of it)
+  auto reads = [&](size_t j, int buf) { return m->ops[j].kind != JG_OP_NMD_FINAL && jg_op_reads(m->ops[j], buf); };
   bool cvt_overflow = false;
   auto need = [&](size_t i, int buf, bool want_f32) {   // queue a conversion in front of op i if the slot is in the other format
     if (buf < 0 || is_f32[buf] == want_f32) return;
@@ -649,7 +652,7 @@ int jg_prepare_f16(jg_model *m, const float *weights) {
         bool first_f16s = false, any_reader = false;
         for (size_t j = i + 1; j < m->ops.size(); ++j) {
           if (reads(j, op.out_buf)) { first_f16s = wants_f16s(j, op.out_buf); any_reader = true; break; }
-          if (writes(j, op.out_buf)) break;
+          if (jg_op_writes(m->ops[j], op.out_buf)) break;
         }
         hp.out_f16s = any_reader && first_f16s;
         is_f32[op.out_buf] = !hp.out_f16s;
@@ -664,7 +667,7 @@ int jg_prepare_f16(jg_model *m, const float *weights) {
               if (o.kind == JG_OP_POOL && o.arg == JG_POOL_MAX && o.in_mask == op.out_mask) pool_idx = (int)j;
               else pool_idx = -2;
             }
-            if (writes(j, op.out_buf)) break;
+            if (jg_op_writes(m->ops[j], op.out_buf)) break;
           }
           if (readers == 1 && pool_idx >= 0) {
             hp.pool_op = pool_idx;
@@ -681,13 +684,6 @@ int jg_prepare_f16(jg_model *m, const float *weights) {
           if (op.stages[q].kind == JG_ST_ADD) need(i, op.stages[q].arg, true);
         is_f32[op.out_buf] = true;
         break;
-      case JG_OP_HYENA:
-      case JG_OP_LENGTHATTN:
-      case JG_OP_LOCALATTN:
-      case JG_OP_FRAMEATTN:                             // f32 rows in and out: an F16S producer is converted in front of it
-        need(i, op.in_buf, true);
-        is_f32[op.out_buf] = true;
-        break;
       case JG_OP_MAXPOOL1D:
         hp.pool_f16s = op.in_buf >= 0 && !is_f32[op.in_buf];
         is_f32[op.out_buf] = !hp.pool_f16s;
@@ -699,7 +695,11 @@ int jg_prepare_f16(jg_model *m, const float *weights) {
       case JG_OP_POOL:
         if (m->pool_fused_by[i] < 0) need(i, op.in_buf, true);
         break;
-      default: break;
+      default:
+        if (!jg_op_is_mixer(op.kind)) break;            // f32 rows in and out: an F16S producer is converted in front of it
+        need(i, op.in_buf, true);
+        is_f32[op.out_buf] = true;
+        break;
     }
   }
   if (cvt_overflow) {
@@ -725,22 +725,6 @@ int jg_plan_phase_split(jg_model *m, const float *weights) {
   static const bool off = jg_exp_env("JG_NO_PSPLIT") != nullptr;
   if (off) return JG_OK;
   const size_t n = m->ops.size();
-  auto reads_buf = [&](size_t j, int buf) {
-    const jg_op &o = m->ops[j];
-    if ((o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-         o.kind == JG_OP_POOL || o.kind == JG_OP_NMD_FINAL || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN || o.kind == JG_OP_HYENA) && o.in_buf == buf)
-      return true;
-    if (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE)
-      for (int q = 0; q < o.n_stages; ++q)
-        if (o.stages[q].kind == JG_ST_ADD && o.stages[q].arg == buf) return true;
-    return false;
-  };
-  auto writes_buf = [&](size_t j, int buf) {
-    const jg_op &o = m->ops[j];
-    return (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-            o.kind == JG_OP_EMBED || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN || o.kind == JG_OP_HYENA) &&
-           o.out_buf == buf;
-  };
   for (size_t p = 0; p < n; ++p) {
     const jg_op &po = m->ops[p];
     ConvHPrep &pp = m->hprep[p];
@@ -752,7 +736,7 @@ int jg_plan_phase_split(jg_model *m, const float *weights) {
     bool ok = true, mask_rewritten = false;
     for (size_t j = p + 1; j < n && ok; ++j) {
       const jg_op &o = m->ops[j];
-      if (reads_buf(j, po.out_buf)) {
+      if (jg_op_reads(m->ops[j], po.out_buf)) {
         const ConvHPrep &hr = m->hprep[j];
         const bool conv_reader = o.kind == JG_OP_CONV && o.in_buf == po.out_buf && hr.f16_ok && o.stride == 2 &&
                                  o.padding == JG_PAD_SAME && o.cin == po.cout && o.in_mask == po.out_mask &&
@@ -766,7 +750,7 @@ int jg_plan_phase_split(jg_model *m, const float *weights) {
         else readers.push_back(j);
       }
       if (o.kind == JG_OP_MASK && po.out_mask >= 0 && o.out_mask == po.out_mask) mask_rewritten = true;
-      if (writes_buf(j, po.out_buf)) break;
+      if (jg_op_writes(m->ops[j], po.out_buf)) break;
     }
     if (!ok || readers.empty()) continue;
     // weights of the 5-tap readers, re-arranged for both parities of the input length
@@ -829,22 +813,6 @@ int jg_plan_resblocks(jg_model *m, const float *weights) {
   static const bool off = jg_exp_env("JG_NO_RESBLOCK") != nullptr;
   if (off) return JG_OK;
   const size_t n = m->ops.size();
-  auto reads_buf = [&](size_t j, int buf) {
-    const jg_op &o = m->ops[j];
-    if ((o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-         o.kind == JG_OP_POOL || o.kind == JG_OP_NMD_FINAL || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN || o.kind == JG_OP_HYENA) && o.in_buf == buf)
-      return true;
-    if (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE)
-      for (int q = 0; q < o.n_stages; ++q)
-        if (o.stages[q].kind == JG_ST_ADD && o.stages[q].arg == buf) return true;
-    return false;
-  };
-  auto writes_buf = [&](size_t j, int buf) {
-    const jg_op &o = m->ops[j];
-    return (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM ||
-            o.kind == JG_OP_EMBED || o.kind == JG_OP_FRAMEATTN || o.kind == JG_OP_LOCALATTN || o.kind == JG_OP_LENGTHATTN || o.kind == JG_OP_HYENA) &&
-           o.out_buf == buf;
-  };
   // bias / batch-norm stages in front of the first other stage, folded with the weights' un-scale (as prepare_f16 does)
   auto fold = [&](const jg_op &op, float acc_scale, float *sc, float *sh) {
     std::vector<double> s((size_t)op.cout, (double)acc_scale), t((size_t)op.cout, 0.0);
@@ -876,12 +844,12 @@ int jg_plan_resblocks(jg_model *m, const float *weights) {
     size_t ib = n;
     bool ok = true;
     for (size_t j = ia + 1; j < n; ++j) {
-      if (reads_buf(j, A.out_buf)) {
+      if (jg_op_reads(m->ops[j], A.out_buf)) {
         if (ib == n && m->ops[j].kind == JG_OP_CONV && m->ops[j].in_buf == A.out_buf) ib = j;
         else ok = false;
       }
-      if (writes_buf(j, A.out_buf) && j != ib) break;
-      if (writes_buf(j, A.out_buf) && j == ib) { ok = false; break; }       // (in place: not a residual block)
+      if (jg_op_writes(m->ops[j], A.out_buf) && j != ib) break;
+      if (jg_op_writes(m->ops[j], A.out_buf) && j == ib) { ok = false; break; }       // (in place: not a residual block)
     }
     if (!ok || ib == n) continue;
     for (size_t j = ia + 1; j < ib && ok; ++j)                               // nothing but mask ops between the two

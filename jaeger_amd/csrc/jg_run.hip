@@ -42,9 +42,7 @@ Place jg_place_op(const jg_model *m, size_t i, const PlaceCtx &c) {
     if (c.fuse_rb && hp.rb_first >= 0) return op.cout == 64 ? PL_RB64 : PL_RB32;
     return PL_CONV_F16;
   }
-  if (op.kind == JG_OP_LOCALATTN) return PL_LOCALATTN;
-  if (op.kind == JG_OP_LENGTHATTN) return PL_LENGTHATTN;
-  if (op.kind == JG_OP_HYENA) return PL_HYENA;
+  if (jg_op_is_mixer(op.kind)) return PL_MIXER;
   if (op.kind == JG_OP_POOL && c.prec == 1 && m->pool_fused_by[i] >= 0) return PL_POOL_FUSED;
   return PL_ORDINARY;
 }
@@ -142,11 +140,12 @@ static int convert_layouts(jg_model *m, size_t i, const OpShape &r, int nw, hipS
     const int slot = hq.cvt_slot[q];
     const Shape &t = r.cvt[q];
     const int64_t rows = (int64_t)nw * t.frames;
-    // (the conversion in front of a frame-attention op is timed as a class of its own: what a kernel variant that
-    // reads F16S directly would save)
-    const bool timed = e->profile && (m->ops[i].kind == JG_OP_FRAMEATTN || m->ops[i].kind == JG_OP_LOCALATTN);
+    // (the conversion in front of a row mixer with a profiling class is timed as a class of its own: what a kernel
+    // variant that reads F16S directly would save)
+    const MixerKind *mk = jg_mixer_kind(m->ops[i].kind);
+    const bool timed = e->profile && mk != nullptr && mk->prof_cvt >= 0;
     ProfEvent pe;
-    int rc = timed ? prof_begin(e, s, m->ops[i].kind == JG_OP_LOCALATTN ? JG_PROF_LOCALATTN_CVT : JG_PROF_FRAMEATTN_CVT, 0.0, &pe) : JG_OK;
+    int rc = timed ? prof_begin(e, s, mk->prof_cvt, 0.0, &pe) : JG_OK;
     if (rc != JG_OK) return rc;
     if (hq.cvt_to_f32[q]) rc = jg_launch_f16s_to_f32(reinterpret_cast<const uint4 *>(m->act[slot]), rows, t.L, t.C, m->cvt_scratch, s);
     else rc = jg_launch_f32_to_f16s(m->act[slot], rows, t.L, t.C, reinterpret_cast<uint4 *>(m->cvt_scratch), s, m->d_overflow);
@@ -403,84 +402,68 @@ static int launch_eltwise(jg_model *m, size_t i, const OpShape &r, int nw, hipSt
   return jg_launch_eltwise(a, s);
 }
 
-static int launch_frameattn(jg_model *m, size_t i, const OpShape &r, int nw, hipStream_t s) {
+// the fields the row mixers' argument structs share (frame attention counts windows and has no mask)
+static void mixer_rows(JgFrameAttnArgs &a, const uint8_t *, int nw, int) { a.n_win = nw; }
+template <typename Args>
+static void mixer_rows(Args &a, const uint8_t *mask, int nw, int frames) {
+  a.mask = mask;
+  a.rows = nw * frames;
+}
+template <typename Args>
+static void mixer_args(const jg_model *m, const jg_op &op, const OpShape &r, int nw, int tile, Args &a) {
+  memset(&a, 0, sizeof(a));
+  a.x = m->act[op.in_buf];
+  a.y = m->act[op.out_buf];
+  a.w = m->d_w + op.w_off;
+  mixer_rows(a, op.in_mask >= 0 ? m->msk[op.in_mask] : nullptr, nw, r.in.frames);
+  a.L = r.in.L; a.tiles = (r.in.L + tile - 1) / tile;
+  a.C = op.cin;
+  a.eps = op.f0;
+  resolve_stages(m, op, a.st, &a.n_stages);
+}
+
+// A row mixer: f32 rows from in_buf to out_buf, validity from the op's mask slot (which it leaves as it is).  Length attention
+// and hyena have no profiling class (scripts/lengthattn_perf.py and scripts/hyena_perf.py time them with events around whole
+// programs); hyena's p_0 .. p_order go through the model's projection scratch (jg_ensure_workspace sized it from the shape walk)
+static int launch_mixer(jg_model *m, size_t i, const OpShape &r, int nw, hipStream_t s) {
   jg_engine *e = m->e;
   const jg_op &op = m->ops[i];
-  JgFrameAttnArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = m->act[op.in_buf];
-  a.y = m->act[op.out_buf];
-  a.w = m->d_w + op.w_off;
-  a.n_win = nw; a.L = r.in.L; a.tiles = (r.in.L + 15) / 16;
-  a.C = op.cin; a.H = op.k; a.D = op.cin / op.k; a.F = op.arg;
-  a.eps = op.f0;
-  resolve_stages(m, op, a.st, &a.n_stages);
+  const int prof = jg_mixer_kind(op.kind)->prof;
+  const int64_t scratch = (int64_t)nw * r.scratch * (int64_t)sizeof(float);
+  JG_REQUIRE(scratch <= m->hy_cap, JG_ERR_INVALID, "op %zu: hyena scratch of %lld bytes, %lld needed", i, (long long)m->hy_cap, (long long)scratch);
   ProfEvent pe;
-  int rc = prof_begin(e, s, JG_PROF_FRAMEATTN, 2.0 * (4.0 * a.C * a.C + 2.0 * a.C * a.F) * 6.0 * (double)nw * r.in.L, &pe);
+  int rc = prof >= 0 ? prof_begin(e, s, prof, jg_mixer_flops(op, r, nw), &pe) : JG_OK;
   if (rc != JG_OK) return rc;
-  return prof_end(e, s, &pe, jg_launch_frameattn(e, a, s));
-}
-
-// one block of local attention: out of place, key validity from the op's mask slot (which it leaves as it is)
-static int launch_localattn(jg_model *m, size_t i, const OpShape &r, int nw, hipStream_t s) {
-  jg_engine *e = m->e;
-  const jg_op &op = m->ops[i];
-  JgLocalAttnArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = m->act[op.in_buf];
-  a.y = m->act[op.out_buf];
-  a.mask = op.in_mask >= 0 ? m->msk[op.in_mask] : nullptr;
-  a.w = m->d_w + op.w_off;
-  a.rows = nw * r.in.frames; a.L = r.in.L; a.tiles = (r.in.L + JG_LOCALATTN_TILE - 1) / JG_LOCALATTN_TILE;
-  a.C = op.cin; a.H = op.k; a.D = op.cin / op.k; a.F = op.arg;
-  a.half = op.stride;
-  a.eps = op.f0;
-  resolve_stages(m, op, a.st, &a.n_stages);
-  const int hb = (a.half + 15) / 16;
-  const double kv_share = (double)(JG_LOCALATTN_TILE + 32 * hb) / JG_LOCALATTN_TILE;
-  ProfEvent pe;
-  int rc = prof_begin(e, s, JG_PROF_LOCALATTN, 2.0 * ((2.0 + 2.0 * kv_share) * a.C * a.C + 2.0 * a.C * a.F) * (double)a.rows * r.in.L, &pe);
-  if (rc != JG_OK) return rc;
-  return prof_end(e, s, &pe, jg_launch_localattn(e, a, s));
-}
-
-// one TransformerEncoder along the length: out of place, query / key validity from the op's mask slot (left as it is).
-// The op has no profiling class of its own (scripts/lengthattn_perf.py times it with events around whole programs)
-static int launch_lengthattn(jg_model *m, size_t i, const OpShape &r, int nw, hipStream_t s) {
-  const jg_op &op = m->ops[i];
-  JgLengthAttnArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = m->act[op.in_buf];
-  a.y = m->act[op.out_buf];
-  a.mask = op.in_mask >= 0 ? m->msk[op.in_mask] : nullptr;
-  a.w = m->d_w + op.w_off;
-  a.rows = nw * r.in.frames; a.L = r.in.L; a.tiles = (r.in.L + JG_LENGTHATTN_TILE - 1) / JG_LENGTHATTN_TILE;
-  a.C = op.cin; a.H = op.k; a.D = op.cin / op.k; a.F = op.arg;
-  a.eps = op.f0;
-  resolve_stages(m, op, a.st, &a.n_stages);
-  return jg_launch_lengthattn(m->e, a, s);
-}
-
-// one hyena block: out of place, validity from the op's mask slot (left as it is); p_0 .. p_order go through the model's
-// projection scratch (jg_ensure_workspace sized it from the shape walk).  No profiling class of its own
-// (scripts/hyena_perf.py times it with events around whole programs)
-static int launch_hyena(jg_model *m, size_t i, const OpShape &r, int nw, hipStream_t s) {
-  const jg_op &op = m->ops[i];
-  JG_REQUIRE((int64_t)nw * r.scratch * (int64_t)sizeof(float) <= m->hy_cap, JG_ERR_INVALID, "op %zu: hyena scratch of %lld bytes, %lld needed",
-             i, (long long)m->hy_cap, (long long)((int64_t)nw * r.scratch * (int64_t)sizeof(float)));
-  JgHyenaArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = m->act[op.in_buf];
-  a.y = m->act[op.out_buf];
-  a.mask = op.in_mask >= 0 ? m->msk[op.in_mask] : nullptr;
-  a.w = m->d_w + op.w_off;
-  a.scratch = m->hy_scratch;
-  a.rows = nw * r.in.frames; a.L = r.in.L; a.tiles = (r.in.L + JG_HYENA_TILE - 1) / JG_HYENA_TILE;
-  a.C = op.cin; a.order = op.k; a.table_rows = op.stride;
-  a.out_proj = (op.arg & JG_HYENA_OUT_PROJ) != 0; a.normalize = (op.arg & JG_HYENA_NORMALIZE) != 0;
-  a.eps = op.f0;
-  resolve_stages(m, op, a.st, &a.n_stages);
-  return jg_launch_hyena(m->e, a, s);
+  switch (op.kind) {
+    case JG_OP_FRAMEATTN: {
+      JgFrameAttnArgs a;
+      mixer_args(m, op, r, nw, 16, a);
+      a.H = op.k; a.D = op.cin / op.k; a.F = op.arg;
+      rc = jg_launch_frameattn(e, a, s);
+    } break;
+    case JG_OP_LOCALATTN: {
+      JgLocalAttnArgs a;
+      mixer_args(m, op, r, nw, JG_LOCALATTN_TILE, a);
+      a.H = op.k; a.D = op.cin / op.k; a.F = op.arg;
+      a.half = op.stride;
+      rc = jg_launch_localattn(e, a, s);
+    } break;
+    case JG_OP_LENGTHATTN: {
+      JgLengthAttnArgs a;
+      mixer_args(m, op, r, nw, JG_LENGTHATTN_TILE, a);
+      a.H = op.k; a.D = op.cin / op.k; a.F = op.arg;
+      rc = jg_launch_lengthattn(e, a, s);
+    } break;
+    default: {      // JG_OP_HYENA
+      JgHyenaArgs a;
+      mixer_args(m, op, r, nw, JG_HYENA_TILE, a);
+      a.scratch = m->hy_scratch;
+      a.order = op.k; a.table_rows = op.stride;
+      a.out_proj = (op.arg & JG_HYENA_OUT_PROJ) != 0; a.normalize = (op.arg & JG_HYENA_NORMALIZE) != 0;
+      rc = jg_launch_hyena(e, a, s);
+    } break;
+  }
+  return prof >= 0 ? prof_end(e, s, &pe, rc) : rc;
 }
 
 static int launch_nmd_final(jg_model *m, size_t i, const OpShape &r, int nw, hipStream_t s) {
@@ -510,7 +493,6 @@ static int launch_ordinary(jg_model *m, size_t i, const OpShape &r, const uint8_
       return jg_launch_mask(op.in_mask == JG_BUF_IDS ? d_ids : m->msk[op.in_mask], nw * m->id_frames, r.m_in, r.L_out, op.k, op.stride,
                             op.dilation, r.pad_left, op.mask_mode, m->msk[op.out_mask], s);
     case JG_OP_ELTWISE: return launch_eltwise(m, i, r, nw, s);
-    case JG_OP_FRAMEATTN: return launch_frameattn(m, i, r, nw, s);
     case JG_OP_MAXPOOL1D:
       if (m->precision == 1 && m->hprep[i].pool_f16s)
         return jg_launch_maxpool1d_f16s(reinterpret_cast<const uint4 *>(m->act[op.in_buf]), nw * in.frames, in.L, r.L_out, in.C,
@@ -570,9 +552,7 @@ static int run_chunk(jg_model *m, const std::vector<OpShape> &shp, const uint8_t
       case PL_POOL_FUSED:
         rc = jg_launch_pool_final(m->pool_part, m->pool_rows, nw, r.in.C, m->vec[op.out_vec] + op.vec_off, m->vec_w[op.out_vec], s);
         break;
-      case PL_LOCALATTN: rc = launch_localattn(m, i, r, nw, s); break;
-      case PL_LENGTHATTN: rc = launch_lengthattn(m, i, r, nw, s); break;
-      case PL_HYENA: rc = launch_hyena(m, i, r, nw, s); break;
+      case PL_MIXER: rc = launch_mixer(m, i, r, nw, s); break;
       case PL_ORDINARY: rc = launch_ordinary(m, i, r, d_ids, nw, s); break;
     }
     if (rc != JG_OK) return rc;

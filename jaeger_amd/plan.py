@@ -107,21 +107,36 @@ class FrameAttn:
     use_ffn: bool = True           # layers.py:2310
 
 
-#: what the frame-attention kernel (csrc/jg_frameattn.hip) covers
-FRAMEATTN_CHANNELS = (32, 64)
-FRAMEATTN_KEY_DIMS = (4, 8, 16, 32, 64)
-FRAMEATTN_MAX_FF = 256
+@dataclass(frozen=True)
+class AttnKernel:
+    """What one of the attention kernels covers, where they differ."""
+    channels: tuple
+    ff_optional: bool              # feed_forward_dim 0 (no feed-forward half) is allowed
+    max_half: int | None           # the largest half-window, None: no window
 
 
-def frame_attn_limit(channels: int, heads: int, ff_dim: int) -> str | None:
-    """Why the frame-attention kernel cannot run this size, or None."""
-    if channels not in FRAMEATTN_CHANNELS:
-        return f"embed_dim {channels} (the kernel covers {' / '.join(map(str, FRAMEATTN_CHANNELS))} channels)"
-    if heads < 1 or channels % heads or channels // heads not in FRAMEATTN_KEY_DIMS:
+ATTN_KEY_DIMS = (4, 8, 16, 32, 64)
+ATTN_MAX_FF = 256
+LOCALATTN_MAX_HALF = 32
+LENGTHATTN_CHANNELS = (16, 32, 64)
+LENGTHATTN_MAX_FF = ATTN_MAX_FF
+FRAMEATTN = AttnKernel((32, 64), True, None)                             # csrc/jg_frameattn.hip
+LOCALATTN = AttnKernel((16, 32, 64), False, LOCALATTN_MAX_HALF)          # csrc/jg_localattn.hip
+LENGTHATTN = AttnKernel(LENGTHATTN_CHANNELS, False, None)               # csrc/jg_lengthattn.hip
+
+
+def attn_limit(kernel: AttnKernel, channels: int, heads: int, ff_dim: int, half_window: int = 0) -> str | None:
+    """Why the attention kernel cannot run this size, or None."""
+    if channels not in kernel.channels:
+        return f"embed_dim {channels} (the kernel covers {' / '.join(map(str, kernel.channels))} channels)"
+    if heads < 1 or channels % heads or channels // heads not in ATTN_KEY_DIMS:
         return (f"num_heads {heads} at embed_dim {channels} (key_dim = embed_dim / num_heads must be one of "
-                f"{', '.join(map(str, FRAMEATTN_KEY_DIMS))})")
-    if ff_dim and (ff_dim % 16 or not 16 <= ff_dim <= FRAMEATTN_MAX_FF):
-        return f"feed_forward_dim {ff_dim} (a multiple of 16 up to {FRAMEATTN_MAX_FF})"
+                f"{', '.join(map(str, ATTN_KEY_DIMS))})")
+    if (ff_dim or not kernel.ff_optional) and (ff_dim % 16 or not 16 <= ff_dim <= ATTN_MAX_FF):
+        return f"feed_forward_dim {ff_dim} (a multiple of 16 up to {ATTN_MAX_FF})"
+    if kernel.max_half is not None and not 0 <= half_window <= kernel.max_half:
+        return (f"window_size {2 * half_window} or more (the kernel covers half-windows of 0 to {kernel.max_half} "
+                f"positions, window_size up to {2 * kernel.max_half + 1})")
     return None
 
 
@@ -141,27 +156,7 @@ class LocalAttn:
     blocks: int = 1                # num_blocks (:2538)
 
 
-#: what the local-attention kernel (csrc/jg_localattn.hip) covers
-LOCALATTN_CHANNELS = (16, 32, 64)
-LOCALATTN_KEY_DIMS = (4, 8, 16, 32, 64)
-LOCALATTN_MAX_FF = 256
-LOCALATTN_MAX_HALF = 32
 _LOCALATTN_REQUIRED = ("embed_dim", "num_heads", "feed_forward_dim", "window_size")   # no defaults (layers.py:2531-2537)
-
-
-def local_attn_limit(channels: int, heads: int, ff_dim: int, half_window: int) -> str | None:
-    """Why the local-attention kernel cannot run this size, or None."""
-    if channels not in LOCALATTN_CHANNELS:
-        return f"embed_dim {channels} (the kernel covers {' / '.join(map(str, LOCALATTN_CHANNELS))} channels)"
-    if heads < 1 or channels % heads or channels // heads not in LOCALATTN_KEY_DIMS:
-        return (f"num_heads {heads} at embed_dim {channels} (key_dim = embed_dim / num_heads must be one of "
-                f"{', '.join(map(str, LOCALATTN_KEY_DIMS))})")
-    if ff_dim % 16 or not 16 <= ff_dim <= LOCALATTN_MAX_FF:
-        return f"feed_forward_dim {ff_dim} (a multiple of 16 up to {LOCALATTN_MAX_FF})"
-    if not 0 <= half_window <= LOCALATTN_MAX_HALF:
-        return (f"window_size {2 * half_window} or more (the kernel covers half-windows of 0 to {LOCALATTN_MAX_HALF} "
-                f"positions, window_size up to {2 * LOCALATTN_MAX_HALF + 1})")
-    return None
 
 
 @dataclass
@@ -206,28 +201,12 @@ class AxialAttn:
         return FrameAttn(f"{self.name}/block{block}/frame", self.channels, self.heads, self.key_dim, self.ff_dim, True)
 
 
-#: what the length-attention kernel (csrc/jg_lengthattn.hip) covers
-LENGTHATTN_CHANNELS = (16, 32, 64)
-LENGTHATTN_KEY_DIMS = (4, 8, 16, 32, 64)
-LENGTHATTN_MAX_FF = 256
 _ATTN_REQUIRED = ("embed_dim", "num_heads", "feed_forward_dim")                    # no defaults (layers.py:2207-2212, :2420-2425)
 # the constructors' own arguments plus what keras.layers.Layer.__init__ takes: any other key is an unknown keyword there
 _AXIAL_KEYS = {"embed_dim", "num_heads", "feed_forward_dim", "dropout_rate", "num_blocks", "epsilon", "norm_type",
                "alpha_init", "name", "dtype", "trainable"}
 _ENCODER_KEYS = {"embed_dim", "num_heads", "feed_forward_dim", "dropout_rate", "attention_axes", "name", "dtype", "trainable"}
 AXIAL_NORM_TYPES = ("layernorm", "masked_layernorm", "masked_dyt", "masked_batchnorm")
-
-
-def length_attn_limit(channels: int, heads: int, ff_dim: int) -> str | None:
-    """Why the length-attention kernel cannot run this size, or None."""
-    if channels not in LENGTHATTN_CHANNELS:
-        return f"embed_dim {channels} (the kernel covers {' / '.join(map(str, LENGTHATTN_CHANNELS))} channels)"
-    if heads < 1 or channels % heads or channels // heads not in LENGTHATTN_KEY_DIMS:
-        return (f"num_heads {heads} at embed_dim {channels} (key_dim = embed_dim / num_heads must be one of "
-                f"{', '.join(map(str, LENGTHATTN_KEY_DIMS))})")
-    if ff_dim % 16 or not 16 <= ff_dim <= LENGTHATTN_MAX_FF:
-        return f"feed_forward_dim {ff_dim} (a multiple of 16 up to {LENGTHATTN_MAX_FF})"
-    return None
 
 
 @dataclass
@@ -436,7 +415,7 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
             if c != cin:
                 raise UnsupportedLayer(f"{p}: embed_dim {c} != {cin} incoming channels (the layer's residual adds them, "
                                        "layers.py:2367)")
-            why = frame_attn_limit(c, h, f)
+            why = attn_limit(FRAMEATTN, c, h, f)
             if why is not None:
                 raise UnsupportedLayer(f"{p}: cross_frame_attention with {why}")
             out.append(FrameAttn(p, c, h, c // h, f, use_ffn))
@@ -456,7 +435,7 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
             if c != cin:
                 raise UnsupportedLayer(f"{p}: embed_dim {c} != {cin} incoming channels (the layer's residual adds them, "
                                        "layers.py:2619)")
-            why = local_attn_limit(c, h, f, window // 2)
+            why = attn_limit(LOCALATTN, c, h, f, window // 2)
             if why is not None:
                 raise UnsupportedLayer(f"{p}: local_attention with {why}")
             out.append(LocalAttn(p, c, h, c // h, f, window // 2, blocks))
@@ -471,7 +450,7 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
             if c != cin:
                 raise UnsupportedLayer(f"{p}: embed_dim {c} != {cin} incoming channels (the layer's residual adds them, "
                                        "layers.py:2256)")
-            why = length_attn_limit(c, h, f)
+            why = attn_limit(LENGTHATTN, c, h, f)
             if why is not None:
                 raise UnsupportedLayer(f"{p}: {name} with {why}")
             if name == "transformer_encoder":
@@ -492,7 +471,7 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
                 if nt not in AXIAL_NORM_TYPES:
                     raise UnsupportedLayer(f"{p}: axial_attention norm_type {nt!r} (layers.py:2457 raises: one of "
                                            f"{', '.join(AXIAL_NORM_TYPES)})")
-                why = frame_attn_limit(c, h, f)
+                why = attn_limit(FRAMEATTN, c, h, f)
                 if why is not None:
                     raise UnsupportedLayer(f"{p}: axial_attention with {why} (its frame half)")
                 out.append(AxialAttn(p, c, h, c // h, f, blocks, nt, float(cfg.get("epsilon", 1e-6)),

@@ -420,14 +420,44 @@ class _Compiler:
                                    "leaves zeros at positions whose band holds no valid key, where the Keras graph holds "
                                    "values that depend on its version and precision")
 
-    def _length_op(self, a: LengthAttn, in_buf: int, out_buf: int, in_mask: int, out_mask: int, stages: list):
-        op = self._op(L.OP_LENGTHATTN, in_buf=in_buf, out_buf=out_buf, in_mask=in_mask, out_mask=out_mask, k=a.heads,
-                      cin=a.channels, cout=a.channels, arg=a.ff_dim, f0=LENGTH_ATTN_EPSILON,
-                      w_off=self.blob.add(pack_length_attn(a, self.w)))
-        op.n_stages = len(stages)
-        for q, st in enumerate(stages):
-            op.stages[q] = st
-        return op
+    def _frame_op(self, a: FrameAttn, in_buf: int, out_buf: int):
+        return self._op(L.OP_FRAMEATTN, in_buf=in_buf, out_buf=out_buf, in_mask=L.JG_BUF_NONE, out_mask=L.JG_BUF_NONE,
+                        k=a.heads, cin=a.channels, cout=a.channels, arg=a.ff_dim if a.use_ffn else 0,
+                        f0=FRAME_ATTN_EPSILON, w_off=self.blob.add(pack_frame_attn(a, self.w)))
+
+    def _length_op(self, a: LengthAttn, in_buf: int, out_buf: int, in_mask: int, out_mask: int):
+        return self._op(L.OP_LENGTHATTN, in_buf=in_buf, out_buf=out_buf, in_mask=in_mask, out_mask=out_mask, k=a.heads,
+                        cin=a.channels, cout=a.channels, arg=a.ff_dim, f0=LENGTH_ATTN_EPSILON,
+                        w_off=self.blob.add(pack_length_attn(a, self.w)))
+
+    def _emit_mixer(self, layers: list, i: int, what: str, buf: int, mask: int, out_mask: int, build_ops: list):
+        """A row-mixer layer (frame / local / length attention, hyena) at ``layers[i]``: its ops - ``build_ops``, one
+        ``(in_buf, out_buf) -> op`` per op, each into a fresh slot, never in place - with the bias / batch norm / unmasked
+        DyT / activation layers that follow fused into the LAST op's store; a LayerNorm or a masked DyT is cut off into an
+        element-wise op behind it.  ``out_mask``: the mask the layers behind see (the incoming one, or none where the layer
+        drops it).  Returns (index of the next layer, the output slot, the mask behind the fused tail)."""
+        layer = layers[i]
+        stages, pending = [], []
+        i, mask2 = self._fuse_tail(layers, i + 1, stages, out_mask, layer.channels, pending)
+        if pending:
+            raise UnsupportedLayer(f"{layer.name}: an nmd tap directly behind {what} is not supported "
+                                   "(the op's store carries no partial sums)")
+        cut = next((j for j, st in enumerate(stages) if st.kind == L.ST_LN or (st.kind == L.ST_DYT and st.arg == 1)), len(stages))
+        stages, tail = stages[:cut], stages[cut:]
+        for build in build_ops:
+            out = self.bufs.take()
+            op = build(buf, out)
+            if build is build_ops[-1]:
+                op.n_stages = len(stages)
+                for q, st in enumerate(stages):
+                    op.stages[q] = st
+            self.ops.append(op)
+            self.bufs.give(buf)
+            buf = out
+        self._emit_ln_tail(layer.name, tail, out_mask, buf, layer.channels)
+        if out_mask != mask:
+            self.masks.give(mask)
+        return i, buf, mask2
 
     def _flush_nmd(self, pending: list, buf: int):
         for nmd, slot, mask in pending:
@@ -578,95 +608,35 @@ class _Compiler:
                     raise UnsupportedLayer(f"{layer.name}: cross_frame_attention directly on the embedding is not supported")
                 self._refuse_unmasked_reader(f"{layer.name}: cross_frame_attention (it attends over all six frames of a position)")
                 # CrossFrameAttention does not set supports_masking (layers.py:2283-2384): the norm / activation / pool / conv
-                # behind it see NO mask, and the values the network holds at masked positions flow on as they are.  The
-                # norm / activation that follow fuse into the op's store; a LayerNorm is cut off into its own op
-                stages: list = []
-                i, _ = self._fuse_tail(layers, i + 1, stages, L.JG_BUF_NONE, layer.channels, pending)
-                if pending:
-                    raise UnsupportedLayer(f"{layer.name}: an nmd tap directly behind cross_frame_attention is not supported "
-                                           "(the op's store carries no partial sums)")
-                tail = []
-                for j, st in enumerate(stages):
-                    if st.kind == L.ST_LN:
-                        stages, tail = stages[:j], stages[j:]
-                        break
-                out = self.bufs.take()
-                op = self._op(L.OP_FRAMEATTN, in_buf=buf, out_buf=out, in_mask=L.JG_BUF_NONE, out_mask=L.JG_BUF_NONE,
-                              k=layer.heads, cin=layer.channels, cout=layer.channels, arg=layer.ff_dim if layer.use_ffn else 0,
-                              f0=FRAME_ATTN_EPSILON, w_off=self.blob.add(pack_frame_attn(layer, self.w)))
-                op.n_stages = len(stages)
-                for j, st in enumerate(stages):
-                    op.stages[j] = st
-                self.ops.append(op)
-                self._emit_ln_tail(layer.name, tail, L.JG_BUF_NONE, out, layer.channels)
-                self.bufs.give(buf)
-                self.masks.give(mask)
-                buf, mask = out, L.JG_BUF_NONE
+                # behind it see NO mask, and the values the network holds at masked positions flow on as they are
+                i, buf, mask = self._emit_mixer(layers, i, "cross_frame_attention", buf, mask, L.JG_BUF_NONE,
+                                                [lambda src, dst: self._frame_op(layer, src, dst)])
             elif isinstance(layer, LocalAttn):
                 if buf == L.JG_BUF_IDS:
                     raise UnsupportedLayer(f"{layer.name}: local_attention directly on the embedding is not supported")
-                # LocalAttention keeps the mask (supports_masking, compute_mask returns it: layers.py:2550, :2627-2628): the
-                # bias / batch norm / unmasked DyT / activation that follow ride the LAST block's store; a LayerNorm or a
-                # masked DyT is cut off into an element-wise op behind it
+                # LocalAttention keeps the mask (supports_masking, compute_mask returns it: layers.py:2550, :2627-2628)
                 if mask != L.JG_BUF_NONE:
                     self.dead_margin = layer.half_window if self.dead_margin is None else min(self.dead_margin, layer.half_window)
                     self.dead_layer = f"{layer.name} (local_attention)"
-                stages = []
-                i, mask2 = self._fuse_tail(layers, i + 1, stages, mask, layer.channels, pending)
-                if pending:
-                    raise UnsupportedLayer(f"{layer.name}: an nmd tap directly behind local_attention is not supported "
-                                           "(the op's store carries no partial sums)")
-                tail = []
-                for j, st in enumerate(stages):
-                    if st.kind == L.ST_LN or (st.kind == L.ST_DYT and st.arg == 1):
-                        stages, tail = stages[:j], stages[j:]
-                        break
-                # one op per block, never in place (a tile reads its neighbours' positions as its halo): two slots ping-pong
-                for j in range(layer.blocks):
-                    out = self.bufs.take()
-                    op = self._op(L.OP_LOCALATTN, in_buf=buf, out_buf=out, in_mask=mask, out_mask=mask, k=layer.heads,
-                                  cin=layer.channels, cout=layer.channels, arg=layer.ff_dim, stride=layer.half_window,
-                                  f0=LOCAL_ATTN_EPSILON, w_off=self.blob.add(pack_local_attn(layer, j, self.w)))
-                    if j == layer.blocks - 1:
-                        op.n_stages = len(stages)
-                        for q, st in enumerate(stages):
-                            op.stages[q] = st
-                    self.ops.append(op)
-                    self.bufs.give(buf)
-                    buf = out
-                self._emit_ln_tail(layer.name, tail, mask, buf, layer.channels)
-                mask = mask2
+                # one op per block (a tile reads its neighbours' positions as its halo): two slots ping-pong
+                i, buf, mask = self._emit_mixer(layers, i, "local_attention", buf, mask, mask, [
+                    lambda src, dst, j=j: self._op(L.OP_LOCALATTN, in_buf=src, out_buf=dst, in_mask=mask, out_mask=mask, k=layer.heads,
+                                                   cin=layer.channels, cout=layer.channels, arg=layer.ff_dim, stride=layer.half_window,
+                                                   f0=LOCAL_ATTN_EPSILON, w_off=self.blob.add(pack_local_attn(layer, j, self.w)))
+                    for j in range(layer.blocks)])
             elif isinstance(layer, Hyena):
                 # HyenaBlock multiplies by the mask on entry, behind its layer norm and on exit (layers.py:3109-3132): it
                 # reads valid positions only and writes Keras' exact values everywhere - zeros at masked positions.  So it
                 # may stand behind a local_attention with live dead positions, and its output holds none.  It keeps the mask
-                # (supports_masking, :3072).  The bias / batch norm / unmasked DyT / activation that follow ride the op's
-                # store; a LayerNorm or a masked DyT is cut off into an element-wise op behind it
+                # (supports_masking, :3072)
                 if mask == L.JG_BUF_NONE:
                     self._refuse_unmasked_reader(f"{layer.name}: hyena_block without a mask")
                 self.dead_margin = None
-                stages = []
-                i, mask2 = self._fuse_tail(layers, i + 1, stages, mask, layer.channels, pending)
-                if pending:
-                    raise UnsupportedLayer(f"{layer.name}: an nmd tap directly behind hyena_block is not supported "
-                                           "(the op's store carries no partial sums)")
-                tail = []
-                for j, st in enumerate(stages):
-                    if st.kind == L.ST_LN or (st.kind == L.ST_DYT and st.arg == 1):
-                        stages, tail = stages[:j], stages[j:]
-                        break
-                out = self.bufs.take()
-                op = self._op(L.OP_HYENA, in_buf=buf, out_buf=out, in_mask=mask, out_mask=mask, k=layer.order,
-                              cin=layer.channels, cout=layer.channels, stride=hyena_table_rows(layer), f0=HYENA_EPSILON,
-                              arg=(L.HYENA_OUT_PROJ if layer.output_projection else 0) | (L.HYENA_NORMALIZE if layer.filter_normalize else 0),
-                              w_off=self.blob.add(pack_hyena(layer, self.w)))
-                op.n_stages = len(stages)
-                for q, st in enumerate(stages):
-                    op.stages[q] = st
-                self.ops.append(op)
-                self._emit_ln_tail(layer.name, tail, mask, out, layer.channels)
-                self.bufs.give(buf)
-                buf, mask = out, mask2
+                i, buf, mask = self._emit_mixer(layers, i, "hyena_block", buf, mask, mask, [
+                    lambda src, dst: self._op(L.OP_HYENA, in_buf=src, out_buf=dst, in_mask=mask, out_mask=mask, k=layer.order,
+                                              cin=layer.channels, cout=layer.channels, stride=hyena_table_rows(layer), f0=HYENA_EPSILON,
+                                              arg=(L.HYENA_OUT_PROJ if layer.output_projection else 0) | (L.HYENA_NORMALIZE if layer.filter_normalize else 0),
+                                              w_off=self.blob.add(pack_hyena(layer, self.w)))])
             elif isinstance(layer, LengthAttn):
                 if buf == L.JG_BUF_IDS:
                     raise UnsupportedLayer(f"{layer.name}: transformer_encoder directly on the embedding is not supported")
@@ -674,23 +644,9 @@ class _Compiler:
                                              "its input value, and the layer drops the mask)")
                 # TransformerEncoder sees the implicit mask of its input (Keras 3 fills MultiHeadAttention's query_mask /
                 # value_mask from it) and does not set supports_masking: the norm / activation / pool / conv behind it see NO
-                # mask.  They fuse into the op's store; a LayerNorm is cut off into its own op
-                stages = []
-                i, _ = self._fuse_tail(layers, i + 1, stages, L.JG_BUF_NONE, layer.channels, pending)
-                if pending:
-                    raise UnsupportedLayer(f"{layer.name}: an nmd tap directly behind transformer_encoder is not supported "
-                                           "(the op's store carries no partial sums)")
-                tail = []
-                for j, st in enumerate(stages):
-                    if st.kind == L.ST_LN:
-                        stages, tail = stages[:j], stages[j:]
-                        break
-                out = self.bufs.take()
-                self.ops.append(self._length_op(layer, buf, out, mask, L.JG_BUF_NONE, stages))
-                self._emit_ln_tail(layer.name, tail, L.JG_BUF_NONE, out, layer.channels)
-                self.bufs.give(buf)
-                self.masks.give(mask)
-                buf, mask = out, L.JG_BUF_NONE
+                # mask
+                i, buf, mask = self._emit_mixer(layers, i, "transformer_encoder", buf, mask, L.JG_BUF_NONE,
+                                                [lambda src, dst: self._length_op(layer, src, dst, mask, L.JG_BUF_NONE)])
             elif isinstance(layer, AxialAttn):
                 if buf == L.JG_BUF_IDS:
                     raise UnsupportedLayer(f"{layer.name}: axial_attention directly on the embedding is not supported")
@@ -704,11 +660,9 @@ class _Compiler:
                     la, fa, norm = layer.length(j), layer.frame(j), layer.post_norm(j)
                     t1 = self.bufs.take()
                     lm = mask if j == 0 else L.JG_BUF_NONE
-                    self.ops.append(self._length_op(la, buf, t1, lm, lm, []))
+                    self.ops.append(self._length_op(la, buf, t1, lm, lm))
                     t2 = self.bufs.take()
-                    self.ops.append(self._op(L.OP_FRAMEATTN, in_buf=t1, out_buf=t2, in_mask=L.JG_BUF_NONE, out_mask=L.JG_BUF_NONE,
-                                             k=fa.heads, cin=fa.channels, cout=fa.channels, arg=fa.ff_dim, f0=FRAME_ATTN_EPSILON,
-                                             w_off=self.blob.add(pack_frame_attn(fa, self.w))))
+                    self.ops.append(self._frame_op(fa, t1, t2))
                     self.bufs.give(t1)
                     masked_norm = layer.norm_type in ("masked_layernorm", "masked_dyt") and mask != L.JG_BUF_NONE
                     stages = [self._norm_stage(norm, masked_norm), self._stage(L.ST_ADD, arg=buf)]

@@ -1,6 +1,6 @@
 """Where every op runs, pinned: for one model per family and the row lengths that flip a placement
-(placement_cases.py), the launches and FLOPs per profiling class of one forward over 8 windows, ``describe()`` and the
-placement statistics equal golden/placement_census.json exactly.
+(placement_cases.py), the launches and FLOPs per profiling class of one forward over 8 windows, ``describe()``, the
+placement statistics and the model's FLOPs per window equal golden/placement_census.json exactly.
 
 The golden file is recorded by scripts/record_placement_census.py from a library built at the commit BEFORE a change to
 the host code, never from the code under test.  Everything in it is host arithmetic - launch counts are integers, the
@@ -32,6 +32,7 @@ def test_placement_census(golden, name):
     want = golden[name]
     assert got["describe"] == want["describe"]
     assert got["stats"] == want["stats"]
+    assert got["flops_per_window"] == want["flops_per_window"]
     assert sorted(got["runs"]) == sorted(want["runs"])
     for run, classes in want["runs"].items():
         assert got["runs"][run] == classes, (name, run)
