@@ -5,7 +5,7 @@
 struct JgFrameAttnArgs {
   const float *x;          // (n_win * 6, L, C) f32 rows, row = window * 6 + frame
   float *y;                // same geometry (may be x: a tile is read whole before it is written)
-  const float *w;          // packed weights: wqkv [3][C][C] | bqkv [3][C] | wo [C][C] | bo [C] | w1 [C][F] | b1 [F] | w2 [F][C] | b2 [C]
+  const float *w;          // packed weights: JgAttnWeights (jg_mixer_dev.h)
   int n_win, L, tiles;     // tiles = ceil(L / 16) position tiles per window
   int C, H, D, F;          // channels, heads, key_dim = C / H, feed-forward width (0 = no feed-forward half)
   float eps;               // of both layer norms

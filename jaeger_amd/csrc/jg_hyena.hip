@@ -28,53 +28,12 @@
 // zero-filled in LDS and never stored.
 #include "jg_common.h"
 #include "jg_hyena.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "jg_mixer_dev.h"
 
 namespace {
 
 constexpr int T = JG_HYENA_TILE, CH = JG_HYENA_CHUNK, NTHREADS = 256;
 static_assert(T == 64 && CH == 64, "thread mapping of the hyena kernels");
-
-// the activations of jg_kernels.hip: jg_apply_act (tanh-GELU and sigmoid through v_exp_f32 / v_rcp_f32)
-__device__ __forceinline__ float hy_act(float v, int act) {
-  switch (act) {
-    case JG_ACT_GELU_TANH: {
-      const float t = v * (-2.3022082f - 0.10294324f * v * v);   // -2u * log2(e), u = sqrt(2/pi)(x + 0.044715 x^3)
-      return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t));
-    }
-    case JG_ACT_GELU_ERF: return 0.5f * v * erfcf(-v * 0.70710678118654752f);
-    case JG_ACT_RELU: return fmaxf(v, 0.0f);
-    case JG_ACT_TANH: return tanhf(v);
-    case JG_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950f * v));
-    default: return v;
-  }
-}
-
-// the op's stage list on one element of channel c (validate_program refuses the stages that need a mask, another tensor
-// or a reduction behind this op)
-__device__ __forceinline__ float hy_stages(float v, const StageArg *st, int n_stages, int c) {
-  for (int s = 0; s < n_stages; ++s) {
-    const StageArg &g = st[s];
-    switch (g.kind) {
-      case JG_ST_BIAS: v += g.p0[c]; break;
-      case JG_ST_BN: v = g.p2[c] * ((v - g.p0[c]) * g.p1[c]) + g.p3[c]; break;
-      case JG_ST_DYT: v = tanhf(g.f0 * v) * g.p2[c] + g.p3[c]; break;
-      case JG_ST_ACT: v = hy_act(v, g.arg); break;
-      default: break;
-    }
-  }
-  return v;
-}
-
-// acc += A (16 x K, rows `lda` apart in LDS) @ B (K x 16 columns of a row-major matrix, `ldw` floats a row): a k-ordered
-// fmaf chain per element on the exact-f32 matrix cores
-template <int K>
-__device__ __forceinline__ void hy_dense(const float *a_rows, int lda, const float *__restrict__ wcol, int ldw, f32x4 &acc, int n, int j) {
-#pragma unroll
-  for (int k0 = 0; k0 < K; k0 += 4)
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a_rows[n * lda + k0 + j], wcol[(size_t)(k0 + j) * ldw], acc, 0, 0, 0);
-}
 
 // ---- phase 1: p_0 .. p_order of a tile ------------------------------------------------------------------------------
 template <int C>
@@ -86,35 +45,14 @@ __global__ __launch_bounds__(NTHREADS) void hyena_proj_kernel(JgHyenaArgs a) {
   const int L = a.L, row = blockIdx.x / a.tiles, p0 = (blockIdx.x - row * a.tiles) * T;
   const float *__restrict__ xrow = a.x + (size_t)row * L * C;
   const uint8_t *__restrict__ mrow = a.mask != nullptr ? a.mask + (size_t)row * L : nullptr;
-  for (int q = tid; q < T * (C / 4); q += NTHREADS) {
-    const int t = q / (C / 4), c4 = (q - t * (C / 4)) * 4, p = p0 + t;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p < L && (mrow == nullptr || mrow[p] != 0)) v = *reinterpret_cast<const float4 *>(xrow + (size_t)p * C + c4);
-    float *r = xn + t * SX + c4;
-    r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
-  }
+  jg_mixer_load_tile<C, SX, NTHREADS>(xn, T, tid, [=](int t) { return p0 + t < L && (mrow == nullptr || mrow[p0 + t] != 0); },
+                                      [=](int t) { return xrow + (size_t)(p0 + t) * C; });
   for (int t = tid; t < T; t += NTHREADS) {
     const int p = p0 + t;
     valid[t] = p < L && (mrow == nullptr || mrow[p] != 0);
   }
   __syncthreads();
-  // LayerNormalization without gamma / beta, one thread a position: biased variance of the centred values
-  for (int t = tid; t < T; t += NTHREADS) {
-    float *r = xn + t * SX;
-    float sum = 0.f;
-#pragma unroll 8
-    for (int c = 0; c < C; ++c) sum += r[c];
-    const float mean = sum * (1.0f / C);
-    float sq = 0.f;
-#pragma unroll 8
-    for (int c = 0; c < C; ++c) {
-      const float d = r[c] - mean;
-      sq = fmaf(d, d, sq);
-    }
-    const float rstd = 1.0f / sqrtf(sq * (1.0f / C) + a.eps);
-#pragma unroll 8
-    for (int c = 0; c < C; ++c) r[c] = (r[c] - mean) * rstd;
-  }
+  jg_mixer_layernorm<C, NTHREADS>(xn, T, tid, a.eps);
   __syncthreads();
   const float *__restrict__ wp = a.w;                                   // [order + 1][C][C] (input channel, output channel)
   const float *__restrict__ bp = wp + (size_t)(a.order + 1) * C * C;    // [order + 1][C]
@@ -125,12 +63,12 @@ __global__ __launch_bounds__(NTHREADS) void hyena_proj_kernel(JgHyenaArgs a) {
     for (int nb = 0; nb < NB; ++nb) {
       const int col = nb * 16 + n;
       const float bias = bp[k * C + col];
-      f32x4 acc = f32x4{bias, bias, bias, bias};
-      hy_dense<C>(xn + wv * 16 * SX, SX, wp + (size_t)k * C * C + col, C, acc, n, j);
+      f32x4 acc[1] = {f32x4{bias, bias, bias, bias}};
+      jg_mixer_dense<1, C>(xn + wv * 16 * SX, SX, wp + (size_t)k * C * C + col, C, acc, n, j);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int r = wv * 16 + 4 * j + i, p = p0 + r;
-        if (p < L) prow[(size_t)p * C + col] = valid[r] ? acc[i] : 0.f;
+        if (p < L) prow[(size_t)p * C + col] = valid[r] ? acc[0][i] : 0.f;
       }
     }
   }
@@ -152,19 +90,11 @@ __global__ __launch_bounds__(NTHREADS) void hyena_conv_kernel(const float *__res
   for (int p = 0; p < NP; ++p) acc[p] = 0.f;
   for (int s0 = 0; s0 <= t0; s0 += CH) {
     __syncthreads();
-    for (int q = tid; q < CH * (C / 4); q += NTHREADS) {
-      const int t = q / (C / 4), c4 = (q - t * (C / 4)) * 4, p = s0 + t;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (p < L) v = *reinterpret_cast<const float4 *>(zrow + (size_t)p * C + c4);
-      *reinterpret_cast<float4 *>(zl + t * C + c4) = v;
-    }
+    jg_mixer_load_tile<C, C, NTHREADS>(zl, CH, tid, [=](int t) { return s0 + t < L; }, [=](int t) { return zrow + (size_t)(s0 + t) * C; });
     // slice row jr holds lag t0 - s0 - (CH - 1) + jr; lags below zero (the diagonal chunk) and at / behind the table: zeros
-    for (int q = tid; q < HR * (C / 4); q += NTHREADS) {
-      const int jr = q / (C / 4), c4 = (q - jr * (C / 4)) * 4, lag = t0 - s0 - (CH - 1) + jr;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (lag >= 0 && lag < table_rows) v = *reinterpret_cast<const float4 *>(h + (size_t)lag * C + c4);
-      *reinterpret_cast<float4 *>(hl + jr * C + c4) = v;
-    }
+    const int lag0 = t0 - s0 - (CH - 1);
+    jg_mixer_load_tile<C, C, NTHREADS>(hl, HR, tid, [=](int jr) { return lag0 + jr >= 0 && lag0 + jr < table_rows; },
+                                       [=](int jr) { return h + (size_t)(lag0 + jr) * C; });
     __syncthreads();
     float part[NP];
 #pragma unroll
@@ -212,29 +142,21 @@ __global__ __launch_bounds__(NTHREADS) void hyena_out_kernel(JgHyenaArgs a, cons
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = lane & 15, j = lane >> 4;
   const int L = a.L, row = blockIdx.x / a.tiles, p0 = (blockIdx.x - row * a.tiles) * T;
   const float *__restrict__ zrow = z + (size_t)row * L * C;
-  for (int q = tid; q < T * (C / 4); q += NTHREADS) {
-    const int t = q / (C / 4), c4 = (q - t * (C / 4)) * 4, p = p0 + t;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p < L) v = *reinterpret_cast<const float4 *>(zrow + (size_t)p * C + c4);
-    float *r = yl + t * SX + c4;
-    r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
-  }
+  jg_mixer_load_tile<C, SX, NTHREADS>(yl, T, tid, [=](int t) { return p0 + t < L; }, [=](int t) { return zrow + (size_t)(p0 + t) * C; });
   __syncthreads();
   if (a.out_proj) {
     const float *__restrict__ wo = a.w + (size_t)(a.order + 1) * C * C + (size_t)(a.order + 1) * C;   // [C][C]
     const float *__restrict__ bo = wo + (size_t)C * C;                                                // [C]
-    f32x4 acc[NB];
+    f32x4 y[1][NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       const float bias = bo[nb * 16 + n];
-      acc[nb] = f32x4{bias, bias, bias, bias};
-      hy_dense<C>(yl + wv * 16 * SX, SX, wo + nb * 16 + n, C, acc[nb], n, j);
+      f32x4 acc[1] = {f32x4{bias, bias, bias, bias}};
+      jg_mixer_dense<1, C>(yl + wv * 16 * SX, SX, wo + nb * 16 + n, C, acc, n, j);
+      y[0][nb] = acc[0];
     }
     __syncthreads();
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) yl[(wv * 16 + 4 * j + i) * SX + nb * 16 + n] = acc[nb][i];
+    jg_mixer_put<C, 1>(yl + wv * 16 * SX, y, n, j);
     __syncthreads();
   }
   const float *__restrict__ xrow = a.x + (size_t)row * L * C;
@@ -249,10 +171,10 @@ __global__ __launch_bounds__(NTHREADS) void hyena_out_kernel(JgHyenaArgs a, cons
       const float4 xv = *reinterpret_cast<const float4 *>(xrow + (size_t)p * C + c4);
       v = make_float4(r[0] + xv.x, r[1] + xv.y, r[2] + xv.z, r[3] + xv.w);
     }
-    v.x = hy_stages(v.x, a.st, a.n_stages, c4);
-    v.y = hy_stages(v.y, a.st, a.n_stages, c4 + 1);
-    v.z = hy_stages(v.z, a.st, a.n_stages, c4 + 2);
-    v.w = hy_stages(v.w, a.st, a.n_stages, c4 + 3);
+    v.x = jg_mixer_stages(v.x, a.st, a.n_stages, c4);
+    v.y = jg_mixer_stages(v.y, a.st, a.n_stages, c4 + 1);
+    v.z = jg_mixer_stages(v.z, a.st, a.n_stages, c4 + 2);
+    v.w = jg_mixer_stages(v.w, a.st, a.n_stages, c4 + 3);
     *reinterpret_cast<float4 *>(yrow + (size_t)p * C + c4) = v;
   }
 }

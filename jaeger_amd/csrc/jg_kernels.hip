@@ -18,37 +18,14 @@
 #include <type_traits>
 
 #include "jg_common.h"
+#include "jg_mixer_dev.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---------------------------------------------------------------------------
 // small device helpers
 // ---------------------------------------------------------------------------
-// (tanh-GELU and sigmoid through v_exp_f32 / v_rcp_f32 - the formulas of the split-f16 kernels, jg_conv_dev.h -
-// instead of libm's tanhf / expf: 8 instead of ~40 instructions per element; the exact-f32 conv's epilogue was a third
-// of its tile time.  Saturates correctly: 2^t -> 0 or inf gives x or -0.)
-__device__ __forceinline__ float jg_apply_act(float v, int act) {
-  switch (act) {
-    case JG_ACT_GELU_TANH: {
-      // tf.nn.gelu(approximate=True): 0.5x(1+tanh(u)) = x / (1 + e^(-2u)), u = sqrt(2/pi)(x+0.044715x^3)
-      const float t = v * (-2.3022082f - 0.10294324f * v * v);   // -2u * log2(e)
-      return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t));
-    }
-    case JG_ACT_GELU_ERF:
-      return 0.5f * v * erfcf(-v * 0.70710678118654752f);
-    case JG_ACT_RELU:
-      return fmaxf(v, 0.0f);
-    case JG_ACT_TANH:
-      // libm: 1 - 2 / (1 + e^(2v)) cancels for small |v| (relative error 1e-3 at |v| = 1e-4), and this kernel is the safe
-      // path the range guard falls back to; a bare tanh activation is not on any hot path
-      return tanhf(v);
-    case JG_ACT_SIGMOID:
-      return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950f * v));
-    default:
-      return v;
-  }
-}
-
+// (the activation jg_apply_act: jg_mixer_dev.h)
 // Apply the fused stage list to 4 consecutive channels n..n+3 of one position.
 // `o` = flat element offset of channel n in the (rows, L_out, cout) output,
 // `mk` = output mask of the position (1 when the op carries no mask).

@@ -10,7 +10,7 @@ struct JgLengthAttnArgs {
   const float *x;          // (rows, L, C) f32 rows, row = window * frames + frame
   float *y;                // same geometry, NEVER x: every query tile reads the whole row
   const uint8_t *mask;     // (rows, L) query / key validity, nullptr = every position of [0, L) is valid
-  const float *w;          // packed weights, the frame-attention layout: wqkv [3][C][C] | bqkv [3][C] | wo [C][C] | bo [C] | w1 [C][F] | b1 [F] | w2 [F][C] | b2 [C]
+  const float *w;          // packed weights: JgAttnWeights (jg_mixer_dev.h)
   int rows, L, tiles;      // tiles = ceil(L / JG_LENGTHATTN_TILE) per row
   int C, H, D, F;          // channels, heads, key_dim = C / H, feed-forward width
   float eps;               // of both layer norms

@@ -11,8 +11,8 @@
 // position is a valid query and key.
 //
 // A workgroup of four waves owns a tile of T = 128 consecutive queries of one row, wave w the two 16-row blocks
-// [32 w, 32 w + 32).  The dense phases are the mathematics of the frame-attention kernel (jg_frameattn.hip) in the same
-// order on the exact-f32 matrix cores (v_mfma_f32_16x16x4_f32: k-ordered fmaf chains from the bias).  The keys of the
+// [32 w, 32 w + 32).  The dense phases are the shared code of jg_mixer_dev.h (layer norm, dense chain, feed-forward
+// half) on the exact-f32 matrix cores (v_mfma_f32_16x16x4_f32: k-ordered fmaf chains from the bias).  The keys of the
 // row go through LDS in chunks of 64 positions: the four waves load and normalise the chunk's rows and compute k | v
 // for 16 positions each (positions at / behind L are zero-filled and invalid, never read: row r + 1 starts there); v
 // rows of invalid keys are zeroed.  Scores, softmax and context are the FIRST FORM of the design: on the
@@ -26,8 +26,7 @@
 // The op is out of place by construction: every query tile reads the whole row.
 #include "jg_common.h"
 #include "jg_lengthattn.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "jg_mixer_dev.h"
 
 namespace {
 
@@ -35,78 +34,10 @@ constexpr int T = JG_LENGTHATTN_TILE, CH = JG_LENGTHATTN_CHUNK, STEP = JG_LENGTH
 constexpr int NTHREADS = 256;
 static_assert(T == 128 && CH == 64 && STEP == 16 && QB == 2, "thread mapping of lengthattn_kernel");
 
-// the activations of jg_kernels.hip: jg_apply_act (tanh-GELU and sigmoid through v_exp_f32 / v_rcp_f32)
-__device__ __forceinline__ float ga_act(float v, int act) {
-  switch (act) {
-    case JG_ACT_GELU_TANH: {
-      const float t = v * (-2.3022082f - 0.10294324f * v * v);   // -2u * log2(e), u = sqrt(2/pi)(x + 0.044715 x^3)
-      return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t));
-    }
-    case JG_ACT_GELU_ERF: return 0.5f * v * erfcf(-v * 0.70710678118654752f);
-    case JG_ACT_RELU: return fmaxf(v, 0.0f);
-    case JG_ACT_TANH: return tanhf(v);
-    case JG_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950f * v));
-    default: return v;
-  }
-}
-
-// the op's stage list on one element of channel c (validate_program refuses the stages that need a mask, another tensor
-// or a reduction behind this op)
-__device__ __forceinline__ float ga_stages(float v, const StageArg *st, int n_stages, int c) {
-  for (int s = 0; s < n_stages; ++s) {
-    const StageArg &g = st[s];
-    switch (g.kind) {
-      case JG_ST_BIAS: v += g.p0[c]; break;
-      case JG_ST_BN: v = g.p2[c] * ((v - g.p0[c]) * g.p1[c]) + g.p3[c]; break;
-      case JG_ST_DYT: v = tanhf(g.f0 * v) * g.p2[c] + g.p3[c]; break;
-      case JG_ST_ACT: v = ga_act(v, g.arg); break;
-      default: break;
-    }
-  }
-  return v;
-}
-
-// LayerNormalization without gamma / beta (folded into the next kernel), in place on `rows` token rows of xn, one
-// thread a row: biased variance of the centred values, 1 / sqrt(var + eps)
-template <int C>
-__device__ __forceinline__ void ga_layernorm(float *xn, int rows, int tid, float eps) {
-  constexpr int SX = C + 2;
-  for (int t = tid; t < rows; t += NTHREADS) {
-    float *row = xn + t * SX;
-    float sum = 0.f;
-#pragma unroll 8
-    for (int c = 0; c < C; ++c) sum += row[c];
-    const float mean = sum * (1.0f / C);
-    float sq = 0.f;
-#pragma unroll 8
-    for (int c = 0; c < C; ++c) {
-      const float d = row[c] - mean;
-      sq = fmaf(d, d, sq);
-    }
-    const float rstd = 1.0f / sqrtf(sq * (1.0f / C) + eps);
-#pragma unroll 8
-    for (int c = 0; c < C; ++c) row[c] = (row[c] - mean) * rstd;
-  }
-}
-
-// acc[f] += A[block f] (16 x K, rows `lda` apart in LDS) @ B (K x 16 columns of a row-major matrix, `ldw` floats a row):
-// a k-ordered fmaf chain per element on the exact-f32 matrix cores; one B read serves the NBLK token blocks
-template <int NBLK, int K>
-__device__ __forceinline__ void ga_dense(const float *a_rows, int lda, const float *__restrict__ wcol, int ldw,
-                                         f32x4 (&acc)[NBLK], int n, int j) {
-#pragma unroll
-  for (int k0 = 0; k0 < K; k0 += 4) {
-    const float b = wcol[(size_t)(k0 + j) * ldw];
-#pragma unroll
-    for (int f = 0; f < NBLK; ++f)
-      acc[f] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_rows[(f * 16 + n) * lda + k0 + j], b, acc[f], 0, 0, 0);
-  }
-}
-
 template <int C>
 __global__ __launch_bounds__(NTHREADS) void lengthattn_kernel(JgLengthAttnArgs a) {
   extern __shared__ float ga_lds[];
-  constexpr int NB = C / 16, SX = C + 2, SKV = 2 * C, SH = 18;
+  constexpr int NB = C / 16, SX = C + 2, SKV = 2 * C;
   constexpr float LOG2E = 1.44269504f;
   const int D = a.D, F = a.F, H = a.H, L = a.L, SM = 2 * H;
   float *xq = ga_lds;                    // [T][SX]  the queries' rows: LN output, then the context, the feed-forward A operand, the store
@@ -118,26 +49,12 @@ __global__ __launch_bounds__(NTHREADS) void lengthattn_kernel(JgLengthAttnArgs a
   int *qvalid = kvalid + CH;                            // [T]
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = lane & 15, j = lane >> 4;
   const int row = blockIdx.x / a.tiles, p0 = (blockIdx.x - row * a.tiles) * T;
-  // packed weights (program.py: pack_length_attn - the frame-attention layout)
-  const float *__restrict__ wqkv = a.w;                       // [3][C][C]   (q | k | v, input channel, h D + d)
-  const float *__restrict__ bqkv = wqkv + 3 * C * C;          // [3][C]
-  const float *__restrict__ wo = bqkv + 3 * C;                // [C][C]      (h D + d, output channel)
-  const float *__restrict__ bo = wo + C * C;                  // [C]
-  const float *__restrict__ w1 = bo + C;                      // [C][F]
-  const float *__restrict__ b1 = w1 + C * F;                  // [F]
-  const float *__restrict__ w2 = b1 + F;                      // [F][C]
-  const float *__restrict__ b2 = w2 + F * C;                  // [C]
+  const JgAttnWeights w = jg_attn_weights(a.w, C, F);
   const float *__restrict__ xrow = a.x + (size_t)row * L * C;
   const uint8_t *__restrict__ mrow = a.mask != nullptr ? a.mask + (size_t)row * L : nullptr;
 
   // ---- the query tile: token t = position p0 + t of this row; positions at / behind L are zero rows and no queries
-  for (int q = tid; q < T * (C / 4); q += NTHREADS) {
-    const int t = q / (C / 4), c4 = (q - t * (C / 4)) * 4, p = p0 + t;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p < L) v = *reinterpret_cast<const float4 *>(xrow + (size_t)p * C + c4);
-    float *r = xq + t * SX + c4;
-    r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
-  }
+  jg_mixer_load_tile<C, SX, NTHREADS>(xq, T, tid, [=](int t) { return p0 + t < L; }, [=](int t) { return xrow + (size_t)(p0 + t) * C; });
   for (int t = tid; t < T; t += NTHREADS) {
     const int p = p0 + t;
     int ok = p < L;
@@ -149,32 +66,20 @@ __global__ __launch_bounds__(NTHREADS) void lengthattn_kernel(JgLengthAttnArgs a
   // + register = position), in these registers to the store
   float *xq_w = xq + wv * (QB * 16) * SX, *qq_w = qq + wv * (QB * 16) * SX;
   f32x4 xr[QB][NB];
-#pragma unroll
-  for (int f = 0; f < QB; ++f)
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) xr[f][nb][i] = xq_w[(f * 16 + 4 * j + i) * SX + nb * 16 + n];
+  jg_mixer_get<C, QB>(xr, xq_w, n, j);
   __syncthreads();
-  ga_layernorm<C>(xq, T, tid, a.eps);
-#pragma unroll
-  for (int f = 0; f < QB; ++f)
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      const float b = bo[nb * 16 + n];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) xr[f][nb][i] += b;
-    }
+  jg_mixer_layernorm<C, NTHREADS>(xq, T, tid, a.eps);
+  jg_mixer_add_bias<C, QB>(xr, w.bo, n);
   __syncthreads();
   // q of the wave's queries, all heads
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
     const int col = nb * 16 + n;
     f32x4 acc[QB];
-    const float bias = bqkv[col];
+    const float bias = w.bqkv[col];
 #pragma unroll
     for (int f = 0; f < QB; ++f) acc[f] = f32x4{bias, bias, bias, bias};
-    ga_dense<QB, C>(xq_w, SX, wqkv + col, C, acc, n, j);
+    jg_mixer_dense<QB, C>(xq_w, SX, w.wqkv + col, C, acc, n, j);
 #pragma unroll
     for (int f = 0; f < QB; ++f)
 #pragma unroll
@@ -191,13 +96,7 @@ __global__ __launch_bounds__(NTHREADS) void lengthattn_kernel(JgLengthAttnArgs a
   // ---- the keys of the row, a chunk of CH positions at a time
   const int query = tid & (T - 1), hp = tid >> 7;
   for (int c0 = 0; c0 < L; c0 += CH) {
-    for (int q = tid; q < CH * (C / 4); q += NTHREADS) {
-      const int t = q / (C / 4), c4 = (q - t * (C / 4)) * 4, p = c0 + t;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (p < L) v = *reinterpret_cast<const float4 *>(xrow + (size_t)p * C + c4);
-      float *r = xc + t * SX + c4;
-      r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
-    }
+    jg_mixer_load_tile<C, SX, NTHREADS>(xc, CH, tid, [=](int t) { return c0 + t < L; }, [=](int t) { return xrow + (size_t)(c0 + t) * C; });
     for (int t = tid; t < CH; t += NTHREADS) {
       const int p = c0 + t;
       int ok = p < L;
@@ -205,7 +104,7 @@ __global__ __launch_bounds__(NTHREADS) void lengthattn_kernel(JgLengthAttnArgs a
       kvalid[t] = ok;
     }
     __syncthreads();
-    ga_layernorm<C>(xc, CH, tid, a.eps);
+    jg_mixer_layernorm<C, NTHREADS>(xc, CH, tid, a.eps);
     __syncthreads();
     // k | v of the wave's 16 positions; the v row of an invalid key is zero (its probability is an exact 0, and 0 * v
     // must stay 0 whatever lies there)
@@ -215,9 +114,9 @@ __global__ __launch_bounds__(NTHREADS) void lengthattn_kernel(JgLengthAttnArgs a
       for (int nb = 0; nb < NB; ++nb) {
         const int col = nb * 16 + n;
         f32x4 acc[1];
-        const float bias = bqkv[(1 + which) * C + col];
+        const float bias = w.bqkv[(1 + which) * C + col];
         acc[0] = f32x4{bias, bias, bias, bias};
-        ga_dense<1, C>(xc + wv * 16 * SX, SX, wqkv + (size_t)(1 + which) * C * C + col, C, acc, n, j);
+        jg_mixer_dense<1, C>(xc + wv * 16 * SX, SX, w.wqkv + (size_t)(1 + which) * C * C + col, C, acc, n, j);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = wv * 16 + 4 * j + i;
@@ -284,7 +183,7 @@ __global__ __launch_bounds__(NTHREADS) void lengthattn_kernel(JgLengthAttnArgs a
   // output projection of the context onto the residual stream (x + b_o)
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
-    const float *__restrict__ wcol = wo + nb * 16 + n;
+    const float *__restrict__ wcol = w.wo + nb * 16 + n;
 #pragma unroll 4
     for (int k0 = 0; k0 < C; k0 += 4) {
       const float b = wcol[(k0 + j) * C];
@@ -295,105 +194,27 @@ __global__ __launch_bounds__(NTHREADS) void lengthattn_kernel(JgLengthAttnArgs a
   }
   __syncthreads();
 
-  // ---- feed-forward half, 16 hidden columns at a time
-#pragma unroll
-  for (int f = 0; f < QB; ++f)
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) xq_w[(f * 16 + 4 * j + i) * SX + nb * 16 + n] = xr[f][nb][i];
-  __syncthreads();
-  ga_layernorm<C>(xq, T, tid, a.eps);
-#pragma unroll
-  for (int f = 0; f < QB; ++f)
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      const float b = b2[nb * 16 + n];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) xr[f][nb][i] += b;
-    }
-  __syncthreads();
-  for (int hb = 0; hb < F; hb += 16) {
-    f32x4 acc[QB];
-    const float bias = b1[hb + n];
-#pragma unroll
-    for (int f = 0; f < QB; ++f) acc[f] = f32x4{bias, bias, bias, bias};
-    ga_dense<QB, C>(xq_w, SX, w1 + hb + n, F, acc, n, j);
-#pragma unroll
-    for (int f = 0; f < QB; ++f)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) qq_w[(f * 16 + 4 * j + i) * SH + n] = ga_act(acc[f][i], JG_ACT_GELU_TANH);
-    __syncthreads();
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      const float *__restrict__ w2col = w2 + (size_t)hb * C + nb * 16 + n;
-#pragma unroll
-      for (int k0 = 0; k0 < 16; k0 += 4) {
-        const float b = w2col[(k0 + j) * C];
-#pragma unroll
-        for (int f = 0; f < QB; ++f)
-          xr[f][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(qq_w[(f * 16 + n) * SH + k0 + j], b, xr[f][nb], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
+  // ---- feed-forward half: the wave's 32 rows of xq, its hidden columns in its 32 rows of q
+  jg_attn_ffn<C, QB, NTHREADS>(xr, xq, T, xq_w, qq_w, w, F, a.eps, tid, n, j);
 
-  // ---- store, with the stages the compiler fused behind the op: through LDS again, so that a lane quad writes 16
-  // consecutive bytes of a token row; positions at / behind L are not written
-#pragma unroll
-  for (int f = 0; f < QB; ++f)
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) xq_w[(f * 16 + 4 * j + i) * SX + nb * 16 + n] = xr[f][nb][i];
+  // ---- store, with the stages the compiler fused behind the op
+  jg_mixer_put<C, QB>(xq_w, xr, n, j);
   __syncthreads();
   float *__restrict__ yrow = a.y + (size_t)row * L * C;
-  for (int q = tid; q < T * (C / 4); q += NTHREADS) {
-    const int t = q / (C / 4), c4 = (q - t * (C / 4)) * 4, p = p0 + t;
-    if (p >= L) continue;
-    const float *r = xq + t * SX + c4;
-    float4 v;
-    v.x = ga_stages(r[0], a.st, a.n_stages, c4);
-    v.y = ga_stages(r[1], a.st, a.n_stages, c4 + 1);
-    v.z = ga_stages(r[2], a.st, a.n_stages, c4 + 2);
-    v.w = ga_stages(r[3], a.st, a.n_stages, c4 + 3);
-    *reinterpret_cast<float4 *>(yrow + (size_t)p * C + c4) = v;
-  }
+  jg_mixer_store_tile<C, NTHREADS>(xq, T, tid, a.st, a.n_stages, [=](int t) { return p0 + t < L; }, [=](int t) { return yrow + (size_t)(p0 + t) * C; });
 }
 
 template <int C>
 int launch_c(const JgLengthAttnArgs &a, int64_t lds, hipStream_t s) {
-  auto kern = lengthattn_kernel<C>;
-  static int64_t attr_set = 0;           // largest dynamic-LDS size this instantiation was opened for
-  if (lds > attr_set) {
-    JG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = lds;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)a.rows * a.tiles)), dim3(NTHREADS), (size_t)lds, s, a);
-  JG_HIP(hipGetLastError());
-  return JG_OK;
+  static int64_t opened = 0;
+  return jg_mixer_launch(lengthattn_kernel<C>, opened, (int64_t)a.rows * a.tiles, NTHREADS, lds, s, a);
 }
 
 }  // namespace
 
-bool jg_lengthattn_supports(int C, int H, int F, char *why, size_t cap) {
-  if (C != 16 && C != 32 && C != 64) {
-    snprintf(why, cap, "%d channels (the kernel covers 16, 32 and 64)", C);
-    return false;
-  }
-  const int D = H >= 1 && C % H == 0 ? C / H : 0;
-  if (D != 4 && D != 8 && D != 16 && D != 32 && D != 64) {
-    snprintf(why, cap, "%d heads at %d channels (key_dim = channels / heads must be 4, 8, 16, 32 or 64)", H, C);
-    return false;
-  }
-  if (F % 16 != 0 || F < 16 || F > 256) {
-    snprintf(why, cap, "feed-forward width %d (a multiple of 16 up to 256)", F);
-    return false;
-  }
-  return true;
-}
+bool jg_lengthattn_supports(int C, int H, int F, char *why, size_t cap) { return jg_attn_supports(true, false, C, H, F, why, cap); }
 
-int64_t jg_lengthattn_blob_floats(int C, int F) { return (int64_t)4 * C * C + 4 * C + (int64_t)2 * C * F + F + C; }
+int64_t jg_lengthattn_blob_floats(int C, int F) { return jg_attn_blob_floats(C, F); }
 
 int64_t jg_lengthattn_lds_bytes(int C, int H) {
   // (the 32 x 18 hidden columns of a wave fit its 32 rows of q)

@@ -9,7 +9,7 @@ struct JgLocalAttnArgs {
   const float *x;          // (rows, L, C) f32 rows, row = window * 6 + frame
   float *y;                // same geometry, NEVER x: a neighbouring tile reads this tile's positions as its halo
   const uint8_t *mask;     // (rows, L) key validity, nullptr = every position of [0, L) is a key
-  const float *w;          // packed weights, the frame-attention layout: wqkv [3][C][C] | bqkv [3][C] | wo [C][C] | bo [C] | w1 [C][F] | b1 [F] | w2 [F][C] | b2 [C]
+  const float *w;          // packed weights: JgAttnWeights (jg_mixer_dev.h)
   int rows, L, tiles;      // tiles = ceil(L / JG_LOCALATTN_TILE) per row
   int C, H, D, F;          // channels, heads, key_dim = C / H, feed-forward width
   int half;                // query q attends keys k with |q - k| <= half

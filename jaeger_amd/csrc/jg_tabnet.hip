@@ -17,26 +17,13 @@
 
 #include "jg_common.h"
 #include "jg_conv_dev.h"
+#include "jg_mixer_dev.h"      // jg_apply_act
 
 bool jg_tab_mfma_row_fits(int L_out, int k, int dil);
 
 namespace {
 
 constexpr int TM_CT = 4;       // 32-channel tiles per wave (4 waves: up to 512 channels)
-
-__device__ __forceinline__ float tabm_act(float v, int act) {
-  switch (act) {
-    case JG_ACT_GELU_TANH: {
-      const float t = v * (-2.3022082f - 0.10294324f * v * v);
-      return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t));
-    }
-    case JG_ACT_GELU_ERF: return 0.5f * v * erfcf(-v * 0.70710678118654752f);
-    case JG_ACT_RELU: return fmaxf(v, 0.0f);
-    case JG_ACT_TANH: return tanhf(v);
-    case JG_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950f * v));
-    default: return v;
-  }
-}
 
 // (the accumulators and the pool never hold a signalling NaN the pool would have to quiet: plain v_max_f32, no canonicalising copy)
 __device__ __forceinline__ float vmax(float x, float y) {
@@ -87,8 +74,8 @@ __device__ __forceinline__ void tab_fold(float (&pool)[TM_CT], const f32x16 (&ac
     for (int r = 0; r < 16; r += 2) {
       float x = acc[c][r], y = acc[c][r + 1];
       if (!LATE) {
-        x = tabm_act(x + bias[c], act);
-        y = tabm_act(y + bias[c], act);
+        x = jg_apply_act(x + bias[c], act);
+        y = jg_apply_act(y + bias[c], act);
       }
       if (left < 32) {
         x = (r >> 2) * 8 + hh * 4 + (r & 3) < left ? x : (MAXP ? -INFINITY : 0.f);
@@ -188,7 +175,7 @@ __global__ __launch_bounds__(256) void tab_mfma_kernel(JgTabMArgs a) {
       const float o = __shfl_xor(pool[c], 32, 64);
       float v = MAXP ? vmax(pool[c], o) : pool[c] + o;
       const int ch = (w * TM_CT + c) * 32 + n;
-      if (LATE) v = tabm_act(v + bias[c], a.act);
+      if (LATE) v = jg_apply_act(v + bias[c], a.act);
       else if (!MAXP) v = v / (float)a.L_out;
       if (hh == 0 && ch < a.cout) a.out[(size_t)row * a.out_ld + ch] = v;
     }

@@ -102,8 +102,8 @@ def pack_frame_attn(a: FrameAttn, w: dict[str, np.ndarray]) -> np.ndarray:
       norms' gamma / beta go into the q / k / v kernels and into ffn_dense1, the kernel normalises only;
     * MultiHeadAttention multiplies the query by ``1 / sqrt(key_dim)`` behind its bias: into the query's kernel and bias.
 
-    Layout: wqkv [3][C][C] (q | k | v; input channel; h * D + d) | bqkv [3][C] | wo [C][C] (h * D + d; output channel) |
-    bo [C] and, with a feed-forward half, w1 [C][F] | b1 [F] | w2 [F][C] | b2 [C]."""
+    Layout: ``JgAttnWeights`` (csrc/jg_mixer_dev.h), the one view the three attention kernels read the blob through -
+    wqkv | bqkv | wo | bo and, with a feed-forward half, w1 | b1 | w2 | b2."""
     c, h, d = a.channels, a.heads, a.key_dim
     f64 = lambda name: np.asarray(w[f"{a.name}/{name}"], np.float64)
     g1, be1 = f64("attn_norm/gamma"), f64("attn_norm/beta")
@@ -127,7 +127,7 @@ LOCAL_ATTN_EPSILON = 1e-6      # both LayerNormalization layers of a LocalAttent
 
 def pack_local_attn(a: LocalAttn, block: int, w: dict[str, np.ndarray]) -> np.ndarray:
     """The weights of block ``block`` of a LocalAttention layer as the kernel reads them (csrc/jg_localattn.hip):
-    :func:`pack_frame_attn`'s fold and layout - ln1 / ln2 gamma and beta into the q / k / v kernels and into ffn1, the
+    :func:`pack_frame_attn`'s fold and layout (``JgAttnWeights``, csrc/jg_mixer_dev.h) - ln1 / ln2 gamma and beta into the q / k / v kernels and into ffn1, the
     query's ``1 / sqrt(key_dim)`` into its kernel and bias, in float64."""
     p = f"{a.name}/block{block}"
     leaf = {"ln1": "attn_norm", "ln2": "ffn_norm", "ffn1": "ffn_dense1", "ffn2": "ffn_dense2", "mha": "mha"}
@@ -144,7 +144,7 @@ LENGTH_ATTN_EPSILON = 1e-6     # both LayerNormalization layers of a Transformer
 
 def pack_length_attn(a: LengthAttn, w: dict[str, np.ndarray]) -> np.ndarray:
     """The weights of one TransformerEncoder as the kernel reads them (csrc/jg_lengthattn.hip): :func:`pack_frame_attn`'s
-    fold and layout under the same leaf names."""
+    fold and layout (``JgAttnWeights``, csrc/jg_mixer_dev.h) under the same leaf names."""
     return pack_frame_attn(FrameAttn(a.name, a.channels, a.heads, a.key_dim, a.ff_dim, True), w)
 
 
