@@ -162,4 +162,4 @@ def forward(model_cfg: dict, weights: dict, ids: np.ndarray, dtype=torch.float32
     pred = {"average": stack.mean(dim=0), "sum": stack.sum(dim=0), "max": stack.max(dim=0).values,
             "concat": torch.cat(heads, dim=-1)}[method]                                 # builder.py:1251-1265
     out = {"prediction": pred, "embedding": torch.stack(reps).mean(dim=0)}
-    return {k: v.detach().to(torch.float32).numpy() for k, v in out.items()}
+    return {k: v.detach().to(torch.float32).numpy() if dtype == torch.float32 else v.detach().numpy() for k, v in out.items()}

@@ -11,7 +11,7 @@ ONE launch.  Probe windows say where a fault sits: the offender list names the w
 The vector tail (part D): the pool, NMD-finish and first dense kernels of the layer-by-layer path are refused by the tap as
 "outputs already"; here each is evaluated in float64 from the tensors the GPU itself produced (the tapped conv output and
 mask, the GPU's own ``embedding`` / ``nmd``) and compared with the GPU's output vector.  Hidden vector slots (a head's inner
-dense layers, NMD merge projections) have no readback and stay out of scope.
+dense layers, NMD merge projections, the signals, the strand rows) are read through sibling models in tests/test_gpu_head.py.
 """
 import time
 
@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import fused_cases as fc
+import head_cases as hc
 import op_cases as oc
 
 pytestmark = pytest.mark.gpu
@@ -266,19 +267,8 @@ def test_strand_rows_do_not_depend_on_their_workgroup_s_history(device, n_cu, ld
 
 
 # ---- part D: the vector tail from the GPU's own inputs ----------------------------------------------------------------------
-#: Bounds from the number formats, not from the kernels.  An f32 sum of n addends: |error| <= (n - 1) 2^-24 x (sum of |addends|)
-#: whatever the order, and the pooled mean's M is that sum over the count: gamma = n 2^-24 bounds a pool / tap mean of n
-#: positions (a dense layer of n inputs: n + 1 addends); rounding errors of independent additions add up like a random walk:
-#: RMS <= (sqrt(n) + 1) 2^-24.  Split-f16: a sum taken in the conv kernel sees the values before they are stored as F16S
-#: (hi + lo keeps 22 bits): + 2^-21 on both.  A maximum of stored values is exact.
-def _gamma_sum(n: int, precision: str = "f32") -> float:
-    return n * 2.0 ** -24 + (2.0 ** -21 if precision == "f16x3" else 0.0)
-
-
-def _rms_sum(n: int, precision: str = "f32") -> float:
-    return (n ** 0.5 + 1.0) * 2.0 ** -24 + (2.0 ** -21 if precision == "f16x3" else 0.0)
-
-
+# (the bounds - head_cases.gamma_sum / rms_sum, from the number formats - and the per-op loop live in tests/head_cases.py, which
+# tests/test_gpu_head.py shares)
 @pytest.mark.parametrize("name,precision,l", [("nmdmerge500", "f32", 100), ("nmdmerge500_max", "f32", 100),
                                               ("nmdmerge500", "f16x3", 300), ("nmdmerge500_max", "f16x3", 300),
                                               ("baseline500_nomask", "f32", 100), ("baseline500_nomaskmax", "f32", 100)])
@@ -287,9 +277,7 @@ def test_vector_tail_from_the_gpu_s_own_tensors(device, name, precision, l):
     tapped output and mask of the last conv, every NMD finish from the tapped output of the conv whose last stage is the tap, and
     the dense layers that read ``embedding`` / ``nmd`` directly, each in float64 from what the GPU produced.  Average and max
     pool, the unmasked pool, an all-masked window (edge_ids window 10), the count + eps divide."""
-    from jaeger_amd import _lib as L
     from jaeger_amd.engine import HipModel
-    from oracle import ops
     from test_gpu_op_taps import Taps
     _, _, prog = fc.compile_small(name)
     model = HipModel(device, prog)
@@ -299,56 +287,7 @@ def test_vector_tail_from_the_gpu_s_own_tensors(device, name, precision, l):
         out = model.forward(ids)
         taps = Taps(model, ids, 0)
         checked = set()
-        for i, op in enumerate(prog.ops):
-            if op.kind == ops.OP_POOL:
-                st = ops.State(ops.program_rows(prog, ids))
-                try:
-                    src = next(j for j in range(i - 1, -1, -1) if prog.ops[j].kind == ops.OP_CONV and prog.ops[j].out_buf == op.in_buf)
-                    st.act[op.in_buf] = taps.get(src)
-                except L.JaegerHipError as exc:          # a store-free conv (fused max pool): tests/test_gpu_op_taps.py's case
-                    assert "store-free" in str(exc), str(exc)
-                    continue
-                mk = taps.mask(i, op.in_mask)
-                if mk is not None:
-                    st.mask[op.in_mask] = mk
-                ref = ops.run_op(prog, i, st)
-                n_pos = st.act[op.in_buf].shape[1] * st.act[op.in_buf].shape[2]
-                got = out["embedding"][:, op.vec_off:op.vec_off + op.cout]
-                res, ok = (fc.check_vec(got, ref.out, ref.M, _gamma_sum(n_pos, precision), _rms_sum(n_pos, precision))
-                           if op.arg == ops.POOL_AVG else fc.check_vec(got, ref.out, ref.M, 0.0, 2.0 ** -24))
-                what = "pool"
-            elif op.kind == ops.OP_NMD_FINAL:
-                src = max(j for j in range(i) if prog.ops[j].kind == ops.OP_CONV
-                          and prog.ops[j].stages[prog.ops[j].n_stages - 1].kind == ops.ST_NMD
-                          and prog.ops[j].stages[prog.ops[j].n_stages - 1].arg == op.arg)
-                st = ops.State(ops.program_rows(prog, ids))
-                try:
-                    st.part[op.arg] = taps.get(src)         # (the tap is the conv's last stage: its stored output is what it saw)
-                except L.JaegerHipError as exc:
-                    assert "store-free" in str(exc), str(exc)
-                    continue
-                mk = taps.mask(i, op.in_mask)
-                if mk is not None:
-                    st.mask[op.in_mask] = mk
-                ref = ops.run_op(prog, i, st)
-                n_pos = st.part[op.arg].shape[1] * st.part[op.arg].shape[2]
-                got = out["nmd"][:, op.vec_off:op.vec_off + op.cout]
-                res, ok = fc.check_vec(got, ref.out, ref.M, _gamma_sum(n_pos, precision), _rms_sum(n_pos, precision))
-                what = "nmd finish"
-            elif op.kind == ops.OP_DENSE and op.in_vec in (ops.VEC_EMBEDDING, ops.VEC_NMD) and op.out_vec in (ops.VEC_PREDICTION, ops.VEC_RELIABILITY):
-                st = ops.State(ops.program_rows(prog, ids))
-                src_name = "embedding" if op.in_vec == ops.VEC_EMBEDDING else "nmd"
-                st.vec[op.in_vec] = out[src_name]
-                ref = ops.run_op(prog, i, st).out
-                w = np.abs(np.asarray(prog.blob[op.w_off:op.w_off + op.cin * op.cout], np.float64)).reshape(op.cin, op.cout)
-                mag = np.abs(out[src_name][:, :op.cin].astype(np.float64)) @ w
-                if op.b_off >= 0:
-                    mag = mag + np.abs(np.asarray(prog.blob[op.b_off:op.b_off + op.cout], np.float64))
-                got = out["prediction" if op.out_vec == ops.VEC_PREDICTION else "reliability"][:, op.vec_off:op.vec_off + op.cout]
-                res, ok = fc.check_vec(got, ref, mag, _gamma_sum(op.cin + 1), _rms_sum(op.cin + 1))
-                what = "dense"
-            else:
-                continue
+        for i, what, res, ok in hc.tail_checks(prog, ids, out, taps, precision):
             checked.add(what)
             _record(f"tail {name} {precision} l={l} op {i} {what}", "", res, len(ids))
             assert ok, fc.report(f"{name} {precision} op {i} ({what})", res)
