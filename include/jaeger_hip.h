@@ -252,7 +252,7 @@ int jg_model_get_precision(const jg_model *m);
  * conversion either side: JG_MSTAT_LAYOUT_CONVERSIONS), JG_MSTAT_SMALL_FUSED = 1 when the whole conv stack runs as the
  * fused small-window kernel.  -1 for an unknown key. */
 enum { JG_MSTAT_CONVS = 0, JG_MSTAT_CONVS_F16X3 = 1, JG_MSTAT_LAYOUT_CONVERSIONS = 2, JG_MSTAT_SMALL_FUSED = 3,
-       JG_MSTAT_TAP_VARIANT = 4 };
+       JG_MSTAT_TAP_VARIANT = 4, JG_MSTAT_TAP_INSTANCE = 5, JG_MSTAT_TAP_INSTANCE_OTHER = 6, JG_MSTAT_CONV_INSTANCE0 = 4096 };
 int64_t jg_model_get_stat(const jg_model *m, int key);
 /* ---- test readback: the tensor one op writes (tests/test_gpu_op_taps.py) ----
  * jg_model_tap_shape: logical shape of what op `op` writes for id rows of l positions, PER WINDOW:
@@ -270,6 +270,27 @@ int64_t jg_model_get_stat(const jg_model *m, int key);
 /* (a frame-attention op reports JG_TAP_EXACT_F32: its one arithmetic; its one layout, f32 rows, has no bit) */
 enum { JG_TAP_F16S = 1, JG_TAP_PHASE_SPLIT = 2, JG_TAP_WINDOW_PACKED = 4, JG_TAP_TABLE_LOOKUP = 8, JG_TAP_NARROW = 16,
        JG_TAP_EXACT_F32 = 32, JG_TAP_FUSED_RESBLOCK = 64 };
+/* JG_MSTAT_TAP_INSTANCE: which instantiation of the split-f16 conv template the tapped conv's launches of the last
+ * jg_forward call ran on (0: none of them was a split-f16 conv launch) - the translation unit ("part": 1 row-tiled
+ * k = 5, 2 row-tiled k = 7 / 9, 3 window-packed, 4 first-layer table variant, 5 / 6 / 7 the 64 / 32-channel and general
+ * 128-wide run-time-geometry tiles of k = 5, 8 .. 10 those of k = 7, 11 .. 13 those of k = 9) and the template
+ * arguments K (0: the table variant), EP (a JG_EP_* stage pattern), FLAT, CW and TANH; for EP = 0xfffe (stage bits at
+ * run time) also those bits.  When the launches of one forward (its launch groups, the 128-channel launches of a wider
+ * conv) ran on different instances the code is that of the first with JG_INST_MIXED set - the codes are never OR-ed -
+ * and JG_MSTAT_TAP_INSTANCE_OTHER is the instance of the last launch that differed from the first (else 0).  A launch the
+ * dispatch has no instance for counts as code 0: followed or preceded by a launch that has one, the forward is "mixed"
+ * (JG_INST_MIXED without JG_INST_VALID when it came first).
+ * JG_MSTAT_CONV_INSTANCE0 + i: the same for conv op i, tapped or not (a store-free conv cannot be tapped), recorded
+ * during forwards that run with a tap set. */
+#define JG_INST_PART_MASK 0xfLL
+#define JG_INST_K_SHIFT 4           /* 4 bits */
+#define JG_INST_EP_SHIFT 8          /* 16 bits */
+#define JG_INST_FLAT (1LL << 24)
+#define JG_INST_TANH (1LL << 25)
+#define JG_INST_CW_SHIFT 26         /* 8 bits */
+#define JG_INST_EP_RT_SHIFT 34      /* 9 bits */
+#define JG_INST_VALID (1LL << 60)
+#define JG_INST_MIXED (1LL << 61)
 int jg_model_tap_shape(const jg_model *m, int op, int32_t l, int64_t shape[4]);
 int jg_model_set_tap(jg_model *m, int op, void *host_dst, int64_t dst_bytes);
 /* ... and conv by conv, as text (one line each: geometry -> kernel; for a conv on the exact-f32 kernel the rule that kept

@@ -30,6 +30,11 @@ JG_COL_STRING, JG_COL_INT, JG_COL_FLOAT, JG_COL_BOOL, JG_COL_SPANS = 0, 1, 2, 3,
 JG_STAT_STREAM_GROUPS, JG_STAT_STREAM_BYTES, JG_STAT_PEAK_DEVICE_BASES, JG_STAT_DUST_MASKED, JG_STAT_WINDOWS_DONE = 1, 2, 3, 4, 5
 JG_MSTAT_CONVS, JG_MSTAT_CONVS_F16X3, JG_MSTAT_LAYOUT_CONVERSIONS, JG_MSTAT_SMALL_FUSED = 0, 1, 2, 3
 JG_MSTAT_TAP_VARIANT = 4
+JG_MSTAT_TAP_INSTANCE, JG_MSTAT_TAP_INSTANCE_OTHER, JG_MSTAT_CONV_INSTANCE0 = 5, 6, 4096
+# JG_MSTAT_TAP_INSTANCE code: the instantiation of the split-f16 conv template a conv's launches ran on (JG_INST_*)
+INST_PART_MASK, INST_K_SHIFT, INST_EP_SHIFT, INST_FLAT, INST_TANH, INST_CW_SHIFT, INST_EP_RT_SHIFT = 0xF, 4, 8, 1 << 24, 1 << 25, 26, 34
+INST_VALID, INST_MIXED = 1 << 60, 1 << 61
+EP_RUNTIME = 0xFFFE            # JG_EP_RUNTIME: the stage bits are run-time arguments (reported beside the instance)
 JG_PROF_MFMA_F16X3, JG_PROF_MFMA_F32, JG_PROF_TABLE, JG_PROF_FUSED_SMALL, JG_PROF_FRAMEATTN, JG_PROF_FRAMEATTN_CVT, JG_PROF_LOCALATTN, JG_PROF_LOCALATTN_CVT = range(8)     # jg_profile_read_class
 # JG_MSTAT_TAP_VARIANT bits: the kernel variant the tapped op ran on (jg_model_set_tap)
 TAP_F16S, TAP_PHASE_SPLIT, TAP_WINDOW_PACKED, TAP_TABLE_LOOKUP, TAP_NARROW, TAP_EXACT_F32, TAP_FUSED_RESBLOCK = 1, 2, 4, 8, 16, 32, 64

@@ -423,7 +423,12 @@ extern "C" int64_t jg_model_get_stat(const jg_model *m, int key) {
     case JG_MSTAT_LAYOUT_CONVERSIONS: return m->f16_eligible ? n_cvt : 0;
     case JG_MSTAT_SMALL_FUSED: return m->small != nullptr ? 1 : 0;
     case JG_MSTAT_TAP_VARIANT: return m->tap_variant;
-    default: return -1;
+    case JG_MSTAT_TAP_INSTANCE: return jg_conv_inst_get(m, -1, false);
+    case JG_MSTAT_TAP_INSTANCE_OTHER: return jg_conv_inst_get(m, -1, true);
+    default:
+      if (key >= JG_MSTAT_CONV_INSTANCE0 && key < JG_MSTAT_CONV_INSTANCE0 + (int)m->ops.size())
+        return jg_conv_inst_get(m, key - JG_MSTAT_CONV_INSTANCE0, false);
+      return -1;
   }
 }
 
@@ -503,6 +508,7 @@ extern "C" int jg_model_destroy(jg_model *m) {
   if (m == nullptr) return JG_OK;
   (void)hipSetDevice(m->e->dev);
   (void)hipStreamSynchronize(m->e->stream);
+  jg_conv_inst_reset(m);
   free_workspace(m);
   jg_free_small(m);
   for (int i = 0; i < JG_MAX_VECS; ++i)

@@ -1,5 +1,9 @@
 // C-ABI of libjaeger_hip.so, forward part: where every op runs (jg_place_op), one launcher per placement, the op-program
 // interpreter that sequences them (run_chunk) and jg_forward.  Host logic only - shapes come from jg_shape_walk.
+#include <map>
+#include <mutex>
+#include <utility>
+
 #include "jg_host.h"
 
 bool jg_tab_mfma_row_fits(int L_out, int k, int dil);       // jg_tabnet.hip: the matrix-core form's id image holds the row
@@ -321,6 +325,50 @@ static void conv_f16_tiling(jg_model *m, size_t i, const OpShape &r, int nw, Con
   if (hp.pool_op >= 0) m->pool_rows = strips_per_win;
 }
 
+// ---- test readback: the template instance of each split-f16 conv launch (JG_MSTAT_TAP_INSTANCE) ----------------------
+// Kept per (model, conv op) while a tap is set: the first launch's instance (0: the dispatch has none for it), whether a
+// later launch of the same forward ran on another one, and that other one.  Host bookkeeping only, behind one mutex (the
+// records of all models share a map; another thread may create, query or destroy its own model meanwhile); an untapped
+// forward records nothing and takes no lock.
+namespace {
+struct ConvInst { bool seen = false; int64_t first = 0, other = 0; };
+std::map<std::pair<const jg_model *, int>, ConvInst> conv_inst;
+std::mutex conv_inst_mu;
+}  // namespace
+
+static void conv_inst_record(const jg_model *m, size_t i, const ConvHArgs &a) {
+  if (m->tap_op < 0) return;
+  const int64_t code = jg_conv_f16_instance(a);
+  std::lock_guard<std::mutex> lock(conv_inst_mu);
+  ConvInst &c = conv_inst[{m, (int)i}];
+  if (!c.seen) { c.seen = true; c.first = code; }
+  else if (code != (c.first & ~JG_INST_MIXED)) { c.first |= JG_INST_MIXED; c.other = code; }
+}
+
+void jg_conv_inst_reset(const jg_model *m) {      // a new forward (or the model goes away): forget the model's records
+  std::lock_guard<std::mutex> lock(conv_inst_mu);
+  auto it = conv_inst.lower_bound({m, -1});      // (-1: the tapped op's index, below)
+  while (it != conv_inst.end() && it->first.first == m) it = conv_inst.erase(it);
+}
+
+static void conv_inst_begin(const jg_model *m) {  // a forward with a tap set: fresh records, and which op is tapped
+  jg_conv_inst_reset(m);
+  std::lock_guard<std::mutex> lock(conv_inst_mu);
+  conv_inst[{m, -1}].first = m->tap_op;
+}
+
+// op = -1: the op that was tapped in the last forward with a tap (the tap itself is off again by the time tests ask)
+int64_t jg_conv_inst_get(const jg_model *m, int op, bool other) {
+  std::lock_guard<std::mutex> lock(conv_inst_mu);
+  if (op < 0) {
+    const auto t = conv_inst.find({m, -1});
+    if (t == conv_inst.end()) return 0;
+    op = (int)t->second.first;
+  }
+  const auto it = conv_inst.find({m, op});
+  return it == conv_inst.end() ? 0 : other ? it->second.other : it->second.first;
+}
+
 static int launch_conv_f16(jg_model *m, size_t i, const OpShape &r, const uint8_t *d_ids, int nw, hipStream_t s) {
   jg_engine *e = m->e;
   const jg_op &op = m->ops[i];
@@ -342,11 +390,13 @@ static int launch_conv_f16(jg_model *m, size_t i, const OpShape &r, const uint8_
   ProfEvent pe;
   int rc = prof_begin(e, s, hp.d_lut != nullptr ? JG_PROF_TABLE : JG_PROF_MFMA_F16X3, conv_flops(op, r, nw), &pe);
   if (rc != JG_OK) return rc;
+  conv_inst_record(m, i, a);
   rc = jg_launch_conv_f16(e, a, s);
   for (int hf = 1; hf < hp.n_half && rc == JG_OK; ++hf) {      // wider than 128 channels: one launch per 128
     a.ch0 = hf * 128;
     a.wh = hp.ps_read == 1 ? hp.d_wh_ps[r.in.L & 1] + (int64_t)hf * hp.ps_half_items : hp.d_wh + (int64_t)hf * hp.wh_half_items;
     a.epi = hp.d_epi + (int64_t)hf * hp.n_epi_rows * 2 * 128;
+    conv_inst_record(m, i, a);
     rc = jg_launch_conv_f16(e, a, s);
   }
   return prof_end(e, s, &pe, rc);
@@ -653,6 +703,7 @@ extern "C" int jg_forward(jg_model *m, const uint8_t *ids, int ids_loc, int64_t 
   JG_HIP(hipSetDevice(e->dev));
   hipStream_t s = pick_stream(e, stream);
   m->tap_variant = 0;
+  if (m->tap_op >= 0) conv_inst_begin(m);
   const uint8_t *d_ids = ids;
   if (ids_loc == JG_PTR_HOST) {
     const int64_t bytes = n_win * m->strands * m->id_frames * (int64_t)l * m->id_bytes;

@@ -340,6 +340,29 @@ class HipModel:
         """``JG_TAP_*`` bits of the kernel variant the last tapped forward ran the op on."""
         return int(self.lib.jg_model_get_stat(self.handle, L.JG_MSTAT_TAP_VARIANT))
 
+    @staticmethod
+    def _decode_instance(code: int) -> dict | None:
+        if not code & (L.INST_VALID | L.INST_MIXED):
+            return None                 # (MIXED without VALID: the first launch had no instance, a later one had - all fields 0)
+        ep = (code >> L.INST_EP_SHIFT) & 0xFFFF
+        return {"part": code & L.INST_PART_MASK, "k": (code >> L.INST_K_SHIFT) & 0xF, "ep": ep,
+                "flat": bool(code & L.INST_FLAT), "cw": (code >> L.INST_CW_SHIFT) & 0xFF, "tanh": bool(code & L.INST_TANH),
+                "ep_rt": (code >> L.INST_EP_RT_SHIFT) & 0x1FF if ep == L.EP_RUNTIME else None,
+                "mixed": bool(code & L.INST_MIXED)}
+
+    def tap_instance(self, op: int | None = None) -> dict | None:
+        """The instantiation of the split-f16 conv template the launches of a conv ran on during the last tapped forward:
+        ``part`` (translation unit), the template arguments ``k`` (0: the table variant), ``ep``, ``flat``, ``cw``, ``tanh``,
+        and ``ep_rt`` (the stage bits of the run-time pattern, else None).  ``mixed``: the launches of that forward did
+        not all run on this instance (it is the first one's; ``other`` is then the last that differed).  ``op`` None: the
+        tapped op; else conv op ``op`` of the same forward (a store-free conv cannot be tapped itself).  None when no
+        launch of the op was a split-f16 conv launch (exact f32, a fused kernel), or when the dispatch has no such instance."""
+        g = lambda k: int(self.lib.jg_model_get_stat(self.handle, k))
+        d = self._decode_instance(g(L.JG_MSTAT_TAP_INSTANCE if op is None else L.JG_MSTAT_CONV_INSTANCE0 + int(op)))
+        if d is not None and op is None:
+            d["other"] = self._decode_instance(g(L.JG_MSTAT_TAP_INSTANCE_OTHER)) if d["mixed"] else None
+        return d
+
     def predict_windows(self, bases, n_bases: int, win_start, win_len, n_win: int, fsize: int, lut,
                         flags: int = 0, l_pad: int | None = None, chunk: int = 0, device_inputs=False,
                         want=("prediction", "reliability", "embedding", "nmd"), counts=True, out: dict | None = None):
