@@ -83,6 +83,78 @@ struct ConvArgs {
 #define JG_EP_GENERIC 0xffffu
 #define JG_EP_RUNTIME 0xfffeu  /* the same canonical stage order with the optional stages behind wave-uniform run-time flags
                                   (ConvHArgs.ep_rt): every canonical stage list without an instantiation of its own */
+// The stage patterns each tiling of the split-f16 conv is compiled for, written once: the switches at the bottom of
+// jg_conv_f16_impl.h (one `case` and its instantiations per entry, in this order - it is the order of the kernels in the
+// code object) and the jg_conv_f16_has_*_pattern predicates (jg_conv_f16.hip) are both generated from these lists.
+// X(ep): the general build only; H(ep): a tanh-GELU build beside the general one (the residual stacks' hot patterns).
+// row-tiled, 128 channels (k = 5, 7 and 9; the tanh-GELU builds are k = 5 only)
+#define JG_CONV_PATTERNS_ROW(X, H)                                                                \
+  X(0u)                                                   /* plain affine: a LayerNorm follows */ \
+  X(JG_EP_NMD1)                                                                                   \
+  H(JG_EP_ACT1)                                                                                   \
+  X(JG_EP_NORM1_AFF | JG_EP_ACT1)                                                                 \
+  X(JG_EP_NORM1_DYT | JG_EP_ACT1)                                                                 \
+  H(JG_EP_ADD | JG_EP_ACT1)                                                                       \
+  X(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1)                                                     \
+  H(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_AFF | JG_EP_ACT2)                           \
+  X(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_DYT | JG_EP_ACT2)         \
+  X(JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ACT1)                                                    \
+  X(JG_EP_NMD1 | JG_EP_NORM1_DYT | JG_EP_ACT1)                                                    \
+  X(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2)                                        \
+  X(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_DYT | JG_EP_ACT2)                      \
+  X(JG_EP_ACT1 | JG_EP_NORM2_AFF)                                                                 \
+  X(JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2)                                                    \
+  X(JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ADD | JG_EP_ACT1)                                        \
+  X(JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2)         \
+  X(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2)                  /* a tap behind a block, no norm after it */ \
+  X(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2)                                        \
+  X(JG_EP_NORM1_DYT)                                                                              \
+  X(JG_EP_RUNTIME)
+// window-packed tiling, k = 5, 128 channels: the stage patterns of the residual stacks
+#define JG_CONV_PATTERNS_FLAT(X, H)                                                               \
+  H(JG_EP_ACT1)                                                                                   \
+  X(JG_EP_NORM1_AFF | JG_EP_ACT1)                                                                 \
+  X(JG_EP_NORM1_DYT | JG_EP_ACT1)                                                                 \
+  H(JG_EP_ADD | JG_EP_ACT1)                                                                       \
+  X(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1)                                                     \
+  H(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_AFF | JG_EP_ACT2)                           \
+  X(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_DYT | JG_EP_ACT2)         \
+  X(JG_EP_ACT1 | JG_EP_NORM2_AFF)                                                                 \
+  X(JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2)                                                    \
+  X(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2)                                        \
+  X(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_DYT | JG_EP_ACT2)                      \
+  X(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2)                                                          \
+  X(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2)                                        \
+  X(JG_EP_RUNTIME)
+// first-layer table variant (a subset of the row-tiled list; the tanh-GELU build is the brain family's first conv)
+#define JG_CONV_PATTERNS_LUT(X, H)                                                                \
+  X(0u)                                                                                           \
+  X(JG_EP_NMD1)                                                                                   \
+  X(JG_EP_ACT1)                                                                                   \
+  X(JG_EP_NORM1_AFF | JG_EP_ACT1)                                                                 \
+  X(JG_EP_NORM1_DYT | JG_EP_ACT1)                                                                 \
+  H(JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ACT1)                                                    \
+  X(JG_EP_NMD1 | JG_EP_NORM1_DYT | JG_EP_ACT1)                                                    \
+  X(JG_EP_ACT1 | JG_EP_NORM2_AFF)                                                                 \
+  X(JG_EP_RUNTIME)
+// run-time output geometry: narrow convs (64 / 32 output channels) and the general 128-wide tile; k = 5 in both tilings,
+// k = 7 and 9 row-tiled
+#define JG_CONV_PATTERNS_GEOM(X)                                                                  \
+  X(0u)                                                                                           \
+  X(JG_EP_ACT1)                                                                                   \
+  X(JG_EP_NORM1_AFF | JG_EP_ACT1)                                                                 \
+  X(JG_EP_ADD | JG_EP_ACT1)                                                                       \
+  X(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2)                                        \
+  X(JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ACT1)                                                    \
+  X(JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ADD | JG_EP_ACT1)                                        \
+  X(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_AFF | JG_EP_ACT2)                           \
+  X(JG_EP_NORM1_DYT | JG_EP_ACT1)                                                                 \
+  X(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1)                                                     \
+  X(JG_EP_NMD1)                                                                                   \
+  X(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2)                                                          \
+  X(JG_EP_NORM1_DYT)                                                                              \
+  X(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2)                                        \
+  X(JG_EP_RUNTIME)
 #define JG_EPI_ROWS 4   /* parameter rows (affine / dyt stages) of a split-f16 epilogue */
 enum { JG_HST_AFFINE = 1, JG_HST_DYT = 2, JG_HST_ADD = 3, JG_HST_ACT = 4, JG_HST_NMD = 5, JG_HST_MASKMUL = 6 };
 struct HStageArg {
@@ -387,7 +459,8 @@ int jg_launch_dust(uint8_t *d_bases, int64_t origin, int64_t span_len, const int
                    int window, int threshold, int64_t own0, int64_t own1, unsigned long long *d_masked, hipStream_t s);
 int jg_conv_tile_m(int l_out);
 int jg_conv_tile_m_for(int l_out, int k, int cin, int stride, int dil);
-int jg_launch_conv_f16(jg_engine *e, const ConvHArgs &a, hipStream_t s);
+// (inst: null, or where the launcher that runs the kernel writes its JG_MSTAT_TAP_INSTANCE code; untouched when nothing is launched)
+int jg_launch_conv_f16(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst);
 int jg_conv_f16_lds_bytes(int k, int dil);
 bool jg_conv_f16_supports(int k, int dil);
 int jg_conv_f16_tile_m(void);

@@ -4,19 +4,19 @@
 
 #include "jg_common.h"
 
-int jg_conv_f16_part_k5(jg_engine *e, const ConvHArgs &a, hipStream_t s);
-int jg_conv_f16_part_k79(jg_engine *e, const ConvHArgs &a, hipStream_t s);
-int jg_conv_f16_part_flat(jg_engine *e, const ConvHArgs &a, hipStream_t s);
-int jg_conv_f16_part_lut(jg_engine *e, const ConvHArgs &a, hipStream_t s);
-int jg_conv_f16_part_n64(jg_engine *e, const ConvHArgs &a, hipStream_t s);
-int jg_conv_f16_part_n32(jg_engine *e, const ConvHArgs &a, hipStream_t s);
-int jg_conv_f16_part_g128(jg_engine *e, const ConvHArgs &a, hipStream_t s);
-int jg_conv_f16_part_x8(jg_engine *e, const ConvHArgs &a, hipStream_t s);     // k = 7: 64 / 32-channel tiles, general tile
-int jg_conv_f16_part_x9(jg_engine *e, const ConvHArgs &a, hipStream_t s);
-int jg_conv_f16_part_x10(jg_engine *e, const ConvHArgs &a, hipStream_t s);
-int jg_conv_f16_part_x11(jg_engine *e, const ConvHArgs &a, hipStream_t s);    // k = 9
-int jg_conv_f16_part_x12(jg_engine *e, const ConvHArgs &a, hipStream_t s);
-int jg_conv_f16_part_x13(jg_engine *e, const ConvHArgs &a, hipStream_t s);
+int jg_conv_f16_part_k5(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst);
+int jg_conv_f16_part_k79(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst);
+int jg_conv_f16_part_flat(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst);
+int jg_conv_f16_part_lut(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst);
+int jg_conv_f16_part_n64(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst);
+int jg_conv_f16_part_n32(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst);
+int jg_conv_f16_part_g128(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst);
+int jg_conv_f16_part_x8(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst);     // k = 7: 64 / 32-channel tiles, general tile
+int jg_conv_f16_part_x9(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst);
+int jg_conv_f16_part_x10(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst);
+int jg_conv_f16_part_x11(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst);    // k = 9
+int jg_conv_f16_part_x12(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst);
+int jg_conv_f16_part_x13(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst);
 #ifdef JG_EXPERIMENT                                                           /* the producer / consumer kernel: experiment build only */
 bool jg_conv_pc_supports(const ConvHArgs &a);                                  // jg_conv_pc.hip
 int jg_conv_pc_launch(jg_engine *e, const ConvHArgs &a, hipStream_t s);
@@ -49,59 +49,31 @@ bool jg_conv_f16_supports(int k, int dil) {
 
 int jg_conv_f16_tile_m(void) { return HM; }
 
-// stage patterns with a compiled epilogue (keep in step with the instantiation sets in jg_conv_f16_impl.h);
-// a first-layer conv may end up on the table variant, which carries a subset
+// stage patterns with a compiled epilogue: the pattern lists of jg_common.h, which the switches of jg_conv_f16_impl.h
+// instantiate entry by entry; a first-layer conv may end up on the table variant, which carries a subset
+#define JG_IS(p) if (ep == (p)) return true;
 bool jg_conv_f16_has_pattern(unsigned ep, bool first_layer) {
-  const unsigned lut[] = {0u, JG_EP_NMD1, JG_EP_ACT1, JG_EP_NORM1_AFF | JG_EP_ACT1, JG_EP_NORM1_DYT | JG_EP_ACT1,
-                          JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ACT1, JG_EP_NMD1 | JG_EP_NORM1_DYT | JG_EP_ACT1,
-                          JG_EP_ACT1 | JG_EP_NORM2_AFF, JG_EP_RUNTIME};
-  const unsigned all[] = {0u, JG_EP_NMD1, JG_EP_ACT1, JG_EP_NORM1_AFF | JG_EP_ACT1, JG_EP_NORM1_DYT | JG_EP_ACT1,
-                          JG_EP_ADD | JG_EP_ACT1, JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1,
-                          JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_AFF | JG_EP_ACT2,
-                          JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_DYT | JG_EP_ACT2,
-                          JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ACT1, JG_EP_NMD1 | JG_EP_NORM1_DYT | JG_EP_ACT1,
-                          JG_EP_ACT1 | JG_EP_NORM2_AFF, JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2,
-                          JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2,
-                          JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_DYT | JG_EP_ACT2,
-                          JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ADD | JG_EP_ACT1,
-                          JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2,
-                          JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2, JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2,
-                          JG_EP_NORM1_DYT, JG_EP_RUNTIME};
-  if (first_layer) {
-    for (unsigned p : lut) if (p == ep) return true;
-    return false;      // (a first layer the table variant cannot take also needs one of `all`: same subset)
+  if (first_layer) {       // (a first layer the table variant cannot take also needs one of the row-tiled list: same subset)
+    JG_CONV_PATTERNS_LUT(JG_IS, JG_IS)
+    return false;
   }
-  for (unsigned p : all) if (p == ep) return true;
+  JG_CONV_PATTERNS_ROW(JG_IS, JG_IS)
   return false;
 }
 
 // stage patterns compiled for the window-packed tiling (jg_conv_f16_part_flat)
 bool jg_conv_f16_has_flat_pattern(unsigned ep) {
-  const unsigned flat[] = {JG_EP_ACT1, JG_EP_NORM1_AFF | JG_EP_ACT1, JG_EP_NORM1_DYT | JG_EP_ACT1, JG_EP_ADD | JG_EP_ACT1,
-                           JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1,
-                           JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_AFF | JG_EP_ACT2,
-                           JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_DYT | JG_EP_ACT2,
-                           JG_EP_ACT1 | JG_EP_NORM2_AFF, JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2,
-                           JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2,
-                           JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_DYT | JG_EP_ACT2,
-                           JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2, JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2, JG_EP_RUNTIME};
-  for (unsigned p : flat) if (p == ep) return true;
+  JG_CONV_PATTERNS_FLAT(JG_IS, JG_IS)
   return false;
 }
 
 // stage patterns compiled for the run-time-geometry variants (narrow convs of 64 / 32 output channels, the general
 // 128-wide tile: jg_conv_f16_part_n64 / _n32 / _g128, k = 5, both tilings)
 bool jg_conv_f16_has_narrow_pattern(unsigned ep) {
-  const unsigned nar[] = {0u, JG_EP_ACT1, JG_EP_NORM1_AFF | JG_EP_ACT1, JG_EP_ADD | JG_EP_ACT1,
-                          JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2, JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ACT1,
-                          JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ADD | JG_EP_ACT1,
-                          JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_AFF | JG_EP_ACT2,
-                          JG_EP_NORM1_DYT | JG_EP_ACT1, JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1, JG_EP_NMD1,
-                          JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2, JG_EP_NORM1_DYT, JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2,
-                          JG_EP_RUNTIME};
-  for (unsigned p : nar) if (p == ep) return true;
+  JG_CONV_PATTERNS_GEOM(JG_IS)
   return false;
 }
+#undef JG_IS
 
 // JG_DBG ablation mask: read at every launch, so that an experiment can warm up on real data and then
 // switch (bench.py --timed-dbg)
@@ -110,7 +82,7 @@ static int jg_dbg_env(void) {
   return ev ? atoi(ev) : 0;
 }
 
-int jg_launch_conv_f16(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
+int jg_launch_conv_f16(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst) {
   JG_REQUIRE(a.cout % 16 == 0 && a.cout_pad == a.cout && a.ch0 % HN == 0 && a.ch0 < a.cout &&
                  (a.cw == HN || ((a.cw == 64 || a.cw == 32) && a.cout <= a.cw && a.ch0 == 0)) &&
                  (a.ostride == 1 || a.ostride == 2) && a.L_res == (a.ostride == 2 ? 2 * a.L_out - 1 : a.L_out),
@@ -125,7 +97,7 @@ int jg_launch_conv_f16(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
                "conv lut: k=%d dilation=%d vocab=%d outside the table variant's limits", a.k, a.dil, a.lut_vocab);
     if (a.rows == 0 || a.L_out <= 0) return JG_OK;
     const_cast<ConvHArgs &>(a).dbg = jg_dbg_env();
-    return jg_conv_f16_part_lut(e, a, s);
+    return jg_conv_f16_part_lut(e, a, s, inst);
   }
   JG_REQUIRE(jg_conv_f16_supports(a.k, a.dil), JG_ERR_UNSUPPORTED,
              "conv_f16x3: k=%d dilation=%d outside the kernel's tiling", a.k, a.dil);
@@ -139,16 +111,16 @@ int jg_launch_conv_f16(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
   const_cast<ConvHArgs &>(a).dbg = jg_dbg_env();
   JG_REQUIRE(!a.lut_one_half, JG_ERR_INVALID, "conv_f16x3: lut_one_half without a table");
   if (a.cw != HN) {
-    if (a.k == 5) return a.cw == 64 ? jg_conv_f16_part_n64(e, a, s) : jg_conv_f16_part_n32(e, a, s);
+    if (a.k == 5) return a.cw == 64 ? jg_conv_f16_part_n64(e, a, s, inst) : jg_conv_f16_part_n32(e, a, s, inst);
     JG_REQUIRE(!a.flat, JG_ERR_UNSUPPORTED, "conv_f16x3: window-packed tiling is only built for k = 5");
-    if (a.k == 7) return a.cw == 64 ? jg_conv_f16_part_x8(e, a, s) : jg_conv_f16_part_x9(e, a, s);
-    return a.cw == 64 ? jg_conv_f16_part_x11(e, a, s) : jg_conv_f16_part_x12(e, a, s);
+    if (a.k == 7) return a.cw == 64 ? jg_conv_f16_part_x8(e, a, s, inst) : jg_conv_f16_part_x9(e, a, s, inst);
+    return a.cw == 64 ? jg_conv_f16_part_x11(e, a, s, inst) : jg_conv_f16_part_x12(e, a, s, inst);
   }
   if (a.cout != HN || a.ostride != 1 || a.tap_lo != 0 || a.tap_hi != a.k - 1 || a.psplit) {     // (ch0 != 0 implies cout > 128; a
                                                                   // phase-split store is built into the run-time-geometry tiles only)
-    if (a.k == 5) return jg_conv_f16_part_g128(e, a, s);
+    if (a.k == 5) return jg_conv_f16_part_g128(e, a, s, inst);
     JG_REQUIRE(!a.flat, JG_ERR_UNSUPPORTED, "conv_f16x3: window-packed tiling is only built for k = 5");
-    return a.k == 7 ? jg_conv_f16_part_x10(e, a, s) : jg_conv_f16_part_x13(e, a, s);
+    return a.k == 7 ? jg_conv_f16_part_x10(e, a, s, inst) : jg_conv_f16_part_x13(e, a, s, inst);
   }
 #ifdef JG_EXPERIMENT
   // the residual stacks' 128 -> 128 five-tap convs on the producer / consumer kernel (math waves + DMA / epilogue helper
@@ -159,8 +131,8 @@ int jg_launch_conv_f16(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
 #endif
   if (a.flat) {
     JG_REQUIRE(a.k == 5 && a.ostride == 1, JG_ERR_UNSUPPORTED, "conv_f16x3: window-packed tiling is only built for k = 5, stride 1");
-    return jg_conv_f16_part_flat(e, a, s);
+    return jg_conv_f16_part_flat(e, a, s, inst);
   }
-  if (a.k == 5) return jg_conv_f16_part_k5(e, a, s);
-  return jg_conv_f16_part_k79(e, a, s);       // 7 or 9: jg_conv_f16_supports() above
+  if (a.k == 5) return jg_conv_f16_part_k5(e, a, s, inst);
+  return jg_conv_f16_part_k79(e, a, s, inst);       // 7 or 9: jg_conv_f16_supports() above
 }

@@ -1454,8 +1454,16 @@ void conv_f16x3_kernel(ConvHArgs a) {
   JG_ST_END;
 }
 
+// the JG_MSTAT_TAP_INSTANCE code (jaeger_hip.h: JG_INST_*) of an instance of the template in this translation unit
+constexpr int64_t pack(int k, unsigned ep, bool flat, int cw, bool tanh, unsigned ep_rt) {
+  return JG_INST_VALID | (int64_t)JG_CONV_PART | ((int64_t)k << JG_INST_K_SHIFT) | ((int64_t)ep << JG_INST_EP_SHIFT) |
+         (flat ? JG_INST_FLAT : 0) | ((int64_t)cw << JG_INST_CW_SHIFT) | (tanh ? JG_INST_TANH : 0) |
+         ((int64_t)(ep == JG_EP_RUNTIME ? (ep_rt & 0x1ffu) : 0u) << JG_INST_EP_RT_SHIFT);
+}
+
+// every launcher below: `inst`, unless null, gets the code of the instance the launch runs on (the test readback of jg_run.hip)
 template <int K, unsigned EP, bool FLAT = false, int CW = 128, bool TANH = false, bool PIPE = false>
-int launch_ke(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
+int launch_ke(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst) {
   const int smem = jg_conv_f16_lds_bytes(K, a.dil);
   static bool attr_set = false;
   if (!attr_set) {
@@ -1472,6 +1480,7 @@ int launch_ke(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
   int grid = ((smem <= 80 * 1024 && !one_wg) ? 2 : 1) * e->n_cu;
   if (grid > n_pairs) grid = n_pairs;
   ConvHArgs b = a;
+  if (inst != nullptr) *inst = pack(K, EP, FLAT, CW, TANH, a.ep_rt);
   hipLaunchKernelGGL((conv_f16x3_kernel<K, EP, false, FLAT, CW, TANH, PIPE>), dim3((unsigned)grid), dim3(HT), (size_t)smem, s, b);
   JG_HIP(hipGetLastError());
 #ifdef JG_STAMP
@@ -1491,20 +1500,20 @@ int launch_ke(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
 // the residual stacks' hot tanh-GELU patterns (k = 5, 128 channels): the pipelined main loop when the engine asks for it
 // (JG_OPT_CONV_PC = 2) and the geometry is the one it is built for
 template <int K, unsigned EP, bool FLAT>
-int launch_hot(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
+int launch_hot(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst) {
   if constexpr (K == 5) {
 #ifdef JG_EXPERIMENT      /* (the pipelined main loop of the producer / consumer experiment: not in the shipped library) */
-    if (e->conv_pc == 2 && a.dil == 3 && a.cc_in % 2 == 0 && a.dbg == 0) return launch_ke<5, EP, FLAT, 128, true, true>(e, a, s);
+    if (e->conv_pc == 2 && a.dil == 3 && a.cc_in % 2 == 0 && a.dbg == 0) return launch_ke<5, EP, FLAT, 128, true, true>(e, a, s, inst);
 #endif
-    return launch_ke<5, EP, FLAT, 128, true>(e, a, s);
+    return launch_ke<5, EP, FLAT, 128, true>(e, a, s, inst);
   } else {
-    return launch_ke<K, EP, FLAT>(e, a, s);
+    return launch_ke<K, EP, FLAT>(e, a, s, inst);
   }
 }
 
 #if JG_CONV_PART == 4
 template <unsigned EP, int CW, bool TANH = false>
-int launch_lut_e(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
+int launch_lut_e(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst) {
   const int smem = jg_conv_lut_lds_bytes(a.k, a.lut_vocab);
   static bool attr_set = false;
   if (!attr_set) {
@@ -1518,155 +1527,95 @@ int launch_lut_e(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
   // (tile group, channel half), one workgroup per CU; a conv of <= 64 channels has only the first half
   const int grid = a.lut_one_half ? (n_pairs < e->n_cu ? n_pairs : e->n_cu)
                                   : 2 * (n_pairs < e->n_cu / 2 ? n_pairs : e->n_cu / 2);
+  if (inst != nullptr) *inst = pack(0, EP, false, CW, TANH, a.ep_rt);      // (K = 0: the table variant takes its taps at run time)
   hipLaunchKernelGGL((conv_f16x3_kernel<0, EP, true, false, CW, TANH>), dim3((unsigned)grid), dim3(JG_LUT_WAVES * 64), (size_t)smem, s, a);
   JG_HIP(hipGetLastError());
   return JG_OK;
 }
-
-int launch_lut(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
-  switch (a.ep) {
-  // 128 output channels: no run-time output geometry; fewer: CW = 129 (channel guards, one table half for <= 64)
-#define JG_CASE(ep) case (ep): return a.cout == 128 ? launch_lut_e<(ep), 128>(e, a, s) : launch_lut_e<(ep), 129>(e, a, s);
-    JG_CASE(0u)
-    JG_CASE(JG_EP_NMD1)
-    JG_CASE(JG_EP_ACT1)
-    JG_CASE(JG_EP_NORM1_AFF | JG_EP_ACT1)
-    JG_CASE(JG_EP_NORM1_DYT | JG_EP_ACT1)
-    case (JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ACT1):       // the brain family's first conv: a tanh-GELU build beside the general one
-      if (a.cout == 128 && a.act_kind == JG_ACT_GELU_TANH) return launch_lut_e<(JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ACT1), 128, true>(e, a, s);
-      return a.cout == 128 ? launch_lut_e<(JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ACT1), 128>(e, a, s)
-                           : launch_lut_e<(JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ACT1), 129>(e, a, s);
-    JG_CASE(JG_EP_NMD1 | JG_EP_NORM1_DYT | JG_EP_ACT1)
-    JG_CASE(JG_EP_ACT1 | JG_EP_NORM2_AFF)
-    JG_CASE(JG_EP_RUNTIME)
-#undef JG_CASE
-    default: break;
-  }
-  jg_set_error("conv lut: stage pattern 0x%x has no compiled epilogue", a.ep);
-  return JG_ERR_UNSUPPORTED;
-}
-
 #endif
 
-// ---- per-translation-unit instantiation sets (JG_CONV_PART selects one; the kernel template is
-// instantiated ~200 times, split over seven objects so that they compile in parallel) -------------
-#define JG_ROW_CASES(K)                                                                              \
-  switch (a.ep) {                                                                                    \
-    case 0u: return launch_ke<K, 0u>(e, a, s);           /* plain affine: a LayerNorm follows */      \
-    case (JG_EP_NMD1): return launch_ke<K, (JG_EP_NMD1)>(e, a, s);                                   \
-    case (JG_EP_ACT1):                                   /* the residual stacks' three hot patterns: tanh-GELU build */ \
-      if (K == 5 && a.act_kind == JG_ACT_GELU_TANH) return launch_hot<K, (JG_EP_ACT1), false>(e, a, s); \
-      return launch_ke<K, (JG_EP_ACT1)>(e, a, s);                                                     \
-    case (JG_EP_NORM1_AFF | JG_EP_ACT1): return launch_ke<K, (JG_EP_NORM1_AFF | JG_EP_ACT1)>(e, a, s); \
-    case (JG_EP_NORM1_DYT | JG_EP_ACT1): return launch_ke<K, (JG_EP_NORM1_DYT | JG_EP_ACT1)>(e, a, s); \
-    case (JG_EP_ADD | JG_EP_ACT1):                                                                   \
-      if (K == 5 && a.act_kind == JG_ACT_GELU_TANH) return launch_hot<K, (JG_EP_ADD | JG_EP_ACT1), false>(e, a, s); \
-      return launch_ke<K, (JG_EP_ADD | JG_EP_ACT1)>(e, a, s);                                         \
-    case (JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1):                                                 \
-      return launch_ke<K, (JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1)>(e, a, s);                      \
-    case (JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_AFF | JG_EP_ACT2):                       \
-      if (K == 5 && a.act_kind == JG_ACT_GELU_TANH)                                                  \
-        return launch_hot<K, (JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_AFF | JG_EP_ACT2), false>(e, a, s); \
-      return launch_ke<K, (JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_AFF | JG_EP_ACT2)>(e, a, s); \
-    case (JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_DYT | JG_EP_ACT2):     \
-      return launch_ke<K, (JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_DYT | JG_EP_ACT2)>(e, a, s); \
-    case (JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ACT1):                                                \
-      return launch_ke<K, (JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ACT1)>(e, a, s);                     \
-    case (JG_EP_NMD1 | JG_EP_NORM1_DYT | JG_EP_ACT1):                                                \
-      return launch_ke<K, (JG_EP_NMD1 | JG_EP_NORM1_DYT | JG_EP_ACT1)>(e, a, s);                     \
-    case (JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2):                                    \
-      return launch_ke<K, (JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2)>(e, a, s);         \
-    case (JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_DYT | JG_EP_ACT2):                  \
-      return launch_ke<K, (JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_DYT | JG_EP_ACT2)>(e, a, s); \
-    case (JG_EP_ACT1 | JG_EP_NORM2_AFF): return launch_ke<K, (JG_EP_ACT1 | JG_EP_NORM2_AFF)>(e, a, s); \
-    case (JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2):                                                \
-      return launch_ke<K, (JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2)>(e, a, s);                     \
-    case (JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ADD | JG_EP_ACT1):                                    \
-      return launch_ke<K, (JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ADD | JG_EP_ACT1)>(e, a, s);         \
-    case (JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2):     \
-      return launch_ke<K, (JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2)>(e, a, s); \
-    case (JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2):           /* a tap behind a block, no norm after it */ \
-      return launch_ke<K, (JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2)>(e, a, s);                           \
-    case (JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2):                                    \
-      return launch_ke<K, (JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2)>(e, a, s);         \
-    case (JG_EP_NORM1_DYT): return launch_ke<K, (JG_EP_NORM1_DYT)>(e, a, s);                         \
-    case (JG_EP_RUNTIME): return launch_ke<K, (JG_EP_RUNTIME)>(e, a, s);                             \
-    default: break;                                                                                  \
-  }                                                                                                  \
-  jg_set_error("conv_f16x3: stage pattern 0x%x has no compiled epilogue", a.ep);                     \
+// ---- per-translation-unit instantiation sets (JG_CONV_PART selects one; the kernel template is instantiated 282 times,
+// split over thirteen objects so that they compile in parallel).  Every switch is one expansion of a pattern list of
+// jg_common.h (JG_CONV_PATTERNS_*): JG_X is the `case` of a pattern with the general build only, JG_H that of a pattern
+// with a tanh-GELU build beside it -------------------------------------------------------------------------------------
+#if JG_CONV_PART == 1 || JG_CONV_PART == 2
+template <int K>
+int launch_row(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst) {
+  switch (a.ep) {
+#define JG_X(ep) case (ep): return launch_ke<K, (ep)>(e, a, s, inst);
+#define JG_H(ep) /* the residual stacks' three hot patterns: the tanh-GELU build is k = 5 only */ \
+  case (ep):                                                                                       \
+    return K == 5 && a.act_kind == JG_ACT_GELU_TANH ? launch_hot<K, (ep), false>(e, a, s, inst) : launch_ke<K, (ep)>(e, a, s, inst);
+    JG_CONV_PATTERNS_ROW(JG_X, JG_H)
+#undef JG_X
+#undef JG_H
+    default: break;
+  }
+  jg_set_error("conv_f16x3: stage pattern 0x%x has no compiled epilogue", a.ep);
   return JG_ERR_UNSUPPORTED;
+}
+#endif
 
 }  // namespace
 
 #if JG_CONV_PART == 1      // row-tiled, k = 5 (the residual stacks)
-int jg_conv_f16_part_k5(jg_engine *e, const ConvHArgs &a, hipStream_t s) { JG_ROW_CASES(5) }
+int jg_conv_f16_part_k5(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst) { return launch_row<5>(e, a, s, inst); }
 #elif JG_CONV_PART == 2    // row-tiled, k = 7 and 9
-int jg_conv_f16_part_k79(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
-  if (a.k == 7) { JG_ROW_CASES(7) }
-  { JG_ROW_CASES(9) }
+int jg_conv_f16_part_k79(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst) {
+  return a.k == 7 ? launch_row<7>(e, a, s, inst) : launch_row<9>(e, a, s, inst);
 }
 #elif JG_CONV_PART == 3    // window-packed tiling, k = 5: the stage patterns of the residual stacks
-int jg_conv_f16_part_flat(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
+int jg_conv_f16_part_flat(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst) {
   switch (a.ep) {
-#define JG_CASE(ep) case (ep): return launch_ke<5, (ep), true>(e, a, s);
-#define JG_CASE_HOT(ep)     /* the residual stacks' hot patterns: a tanh-GELU build beside the general one */ \
-  case (ep):                                                                                                  \
-    return a.act_kind == JG_ACT_GELU_TANH ? launch_hot<5, (ep), true>(e, a, s) : launch_ke<5, (ep), true>(e, a, s);
-    JG_CASE_HOT(JG_EP_ACT1)
-    JG_CASE(JG_EP_NORM1_AFF | JG_EP_ACT1)
-    JG_CASE(JG_EP_NORM1_DYT | JG_EP_ACT1)
-    JG_CASE_HOT(JG_EP_ADD | JG_EP_ACT1)
-    JG_CASE(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1)
-    JG_CASE_HOT(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_AFF | JG_EP_ACT2)
-    JG_CASE(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_DYT | JG_EP_ACT2)
-    JG_CASE(JG_EP_ACT1 | JG_EP_NORM2_AFF)
-    JG_CASE(JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2)
-    JG_CASE(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2)
-    JG_CASE(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_DYT | JG_EP_ACT2)
-    JG_CASE(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2)
-    JG_CASE(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2)
-    JG_CASE(JG_EP_RUNTIME)
-#undef JG_CASE
-#undef JG_CASE_HOT
+#define JG_X(ep) case (ep): return launch_ke<5, (ep), true>(e, a, s, inst);
+#define JG_H(ep)     /* the residual stacks' hot patterns: a tanh-GELU build beside the general one */ \
+  case (ep):                                                                                            \
+    return a.act_kind == JG_ACT_GELU_TANH ? launch_hot<5, (ep), true>(e, a, s, inst) : launch_ke<5, (ep), true>(e, a, s, inst);
+    JG_CONV_PATTERNS_FLAT(JG_X, JG_H)
+#undef JG_X
+#undef JG_H
     default: break;
   }
   jg_set_error("conv_f16x3: stage pattern 0x%x has no compiled window-packed epilogue", a.ep);
   return JG_ERR_UNSUPPORTED;
 }
 #elif JG_CONV_PART == 4    // first-layer table variant
-int jg_conv_f16_part_lut(jg_engine *e, const ConvHArgs &a, hipStream_t s) { return launch_lut(e, a, s); }
+int jg_conv_f16_part_lut(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst) {
+  switch (a.ep) {
+  // 128 output channels: no run-time output geometry; fewer: CW = 129 (channel guards, one table half for <= 64)
+#define JG_GENERAL(ep) return a.cout == 128 ? launch_lut_e<(ep), 128>(e, a, s, inst) : launch_lut_e<(ep), 129>(e, a, s, inst);
+#define JG_X(ep) case (ep): JG_GENERAL(ep)
+#define JG_H(ep)     /* the brain family's first conv: a tanh-GELU build beside the general one */           \
+  case (ep):                                                                                                  \
+    if (a.cout == 128 && a.act_kind == JG_ACT_GELU_TANH) return launch_lut_e<(ep), 128, true>(e, a, s, inst); \
+    JG_GENERAL(ep)
+    JG_CONV_PATTERNS_LUT(JG_X, JG_H)
+#undef JG_GENERAL
+#undef JG_X
+#undef JG_H
+    default: break;
+  }
+  jg_set_error("conv lut: stage pattern 0x%x has no compiled epilogue", a.ep);
+  return JG_ERR_UNSUPPORTED;
+}
 #elif JG_CONV_PART >= 5 && JG_CONV_PART <= 7   // run-time output geometry, k = 5, both tilings: narrow convs (64 / 32
                                                // output channels) and the general 128-wide tile (CW = 129)
 #if JG_CONV_PART == 5
 #define JG_NARROW_CW 64
-int jg_conv_f16_part_n64(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
+int jg_conv_f16_part_n64(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst) {
 #elif JG_CONV_PART == 6
 #define JG_NARROW_CW 32
-int jg_conv_f16_part_n32(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
+int jg_conv_f16_part_n32(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst) {
 #else
 #define JG_NARROW_CW 129
-int jg_conv_f16_part_g128(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
+int jg_conv_f16_part_g128(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst) {
 #endif
   switch (a.ep) {
-#define JG_CASE(ep)                                                          \
+#define JG_X(ep)                                                             \
   case (ep):                                                                 \
-    return a.flat ? launch_ke<5, (ep), true, JG_NARROW_CW>(e, a, s) : launch_ke<5, (ep), false, JG_NARROW_CW>(e, a, s);
-    JG_CASE(0u)
-    JG_CASE(JG_EP_ACT1)
-    JG_CASE(JG_EP_NORM1_AFF | JG_EP_ACT1)
-    JG_CASE(JG_EP_ADD | JG_EP_ACT1)
-    JG_CASE(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2)
-    JG_CASE(JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ACT1)
-    JG_CASE(JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ADD | JG_EP_ACT1)
-    JG_CASE(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_AFF | JG_EP_ACT2)
-    JG_CASE(JG_EP_NORM1_DYT | JG_EP_ACT1)
-    JG_CASE(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1)
-    JG_CASE(JG_EP_NMD1)
-    JG_CASE(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2)
-    JG_CASE(JG_EP_NORM1_DYT)
-    JG_CASE(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2)
-    JG_CASE(JG_EP_RUNTIME)
-#undef JG_CASE
+    return a.flat ? launch_ke<5, (ep), true, JG_NARROW_CW>(e, a, s, inst) : launch_ke<5, (ep), false, JG_NARROW_CW>(e, a, s, inst);
+    JG_CONV_PATTERNS_GEOM(JG_X)
+#undef JG_X
     default: break;
   }
   jg_set_error("conv_f16x3: stage pattern 0x%x has no compiled narrow-conv epilogue", a.ep);
@@ -1678,25 +1627,11 @@ int jg_conv_f16_part_g128(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
 #define JG_X_K ((JG_CONV_PART - 8) / 3 == 0 ? 7 : 9)
 #define JG_X_NAME2(p) jg_conv_f16_part_x##p
 #define JG_X_NAME(p) JG_X_NAME2(p)
-int JG_X_NAME(JG_CONV_PART)(jg_engine *e, const ConvHArgs &a, hipStream_t s) {
+int JG_X_NAME(JG_CONV_PART)(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst) {
   switch (a.ep) {
-#define JG_CASE(ep) case (ep): return launch_ke<JG_X_K, (ep), false, JG_X_CW>(e, a, s);
-    JG_CASE(0u)
-    JG_CASE(JG_EP_ACT1)
-    JG_CASE(JG_EP_NORM1_AFF | JG_EP_ACT1)
-    JG_CASE(JG_EP_ADD | JG_EP_ACT1)
-    JG_CASE(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NORM2_AFF | JG_EP_ACT2)
-    JG_CASE(JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ACT1)
-    JG_CASE(JG_EP_NMD1 | JG_EP_NORM1_AFF | JG_EP_ADD | JG_EP_ACT1)
-    JG_CASE(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2 | JG_EP_NORM2_AFF | JG_EP_ACT2)
-    JG_CASE(JG_EP_NORM1_DYT | JG_EP_ACT1)
-    JG_CASE(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1)
-    JG_CASE(JG_EP_NMD1)
-    JG_CASE(JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2)
-    JG_CASE(JG_EP_NORM1_DYT)
-    JG_CASE(JG_EP_NORM1_DYT | JG_EP_ADD | JG_EP_ACT1 | JG_EP_NMD2)
-    JG_CASE(JG_EP_RUNTIME)
-#undef JG_CASE
+#define JG_X(ep) case (ep): return launch_ke<JG_X_K, (ep), false, JG_X_CW>(e, a, s, inst);
+    JG_CONV_PATTERNS_GEOM(JG_X)
+#undef JG_X
     default: break;
   }
   jg_set_error("conv_f16x3: stage pattern 0x%x has no compiled k = 7 / 9 run-time-geometry epilogue", a.ep);

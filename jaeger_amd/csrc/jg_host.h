@@ -114,7 +114,6 @@ int jg_forward_chunks(jg_model *m, const std::vector<OpShape> &shp, const uint8_
 int jg_forward_device_ids(jg_model *m, const uint8_t *d_ids, int64_t n_win, int l, float *prediction, float *reliability,
                           float *embedding, float *nmd, int out_loc, int chunk, hipStream_t s);
 
-int64_t jg_conv_f16_instance(const ConvHArgs &a);               // jg_conv_inst.hip: the template instance a launch runs on
 void jg_conv_inst_reset(const jg_model *m);                     // jg_run.hip: the per-op records of JG_MSTAT_TAP_INSTANCE
 int64_t jg_conv_inst_get(const jg_model *m, int op, bool other);
 

@@ -336,9 +336,7 @@ std::map<std::pair<const jg_model *, int>, ConvInst> conv_inst;
 std::mutex conv_inst_mu;
 }  // namespace
 
-static void conv_inst_record(const jg_model *m, size_t i, const ConvHArgs &a) {
-  if (m->tap_op < 0) return;
-  const int64_t code = jg_conv_f16_instance(a);
+static void conv_inst_record(const jg_model *m, size_t i, int64_t code) {
   std::lock_guard<std::mutex> lock(conv_inst_mu);
   ConvInst &c = conv_inst[{m, (int)i}];
   if (!c.seen) { c.seen = true; c.first = code; }
@@ -390,14 +388,18 @@ static int launch_conv_f16(jg_model *m, size_t i, const OpShape &r, const uint8_
   ProfEvent pe;
   int rc = prof_begin(e, s, hp.d_lut != nullptr ? JG_PROF_TABLE : JG_PROF_MFMA_F16X3, conv_flops(op, r, nw), &pe);
   if (rc != JG_OK) return rc;
-  conv_inst_record(m, i, a);
-  rc = jg_launch_conv_f16(e, a, s);
-  for (int hf = 1; hf < hp.n_half && rc == JG_OK; ++hf) {      // wider than 128 channels: one launch per 128
-    a.ch0 = hf * 128;
-    a.wh = hp.ps_read == 1 ? hp.d_wh_ps[r.in.L & 1] + (int64_t)hf * hp.ps_half_items : hp.d_wh + (int64_t)hf * hp.wh_half_items;
-    a.epi = hp.d_epi + (int64_t)hf * hp.n_epi_rows * 2 * 128;
-    conv_inst_record(m, i, a);
-    rc = jg_launch_conv_f16(e, a, s);
+  // with a tap set, the launcher that runs names its instance; a dispatch without one fails and is recorded as 0, a call
+  // that launches nothing (an empty batch) returns JG_OK without a code and is not recorded
+  const bool tapped = m->tap_op >= 0;
+  for (int hf = 0; hf < hp.n_half && rc == JG_OK; ++hf) {      // wider than 128 channels: one launch per 128
+    if (hf > 0) {
+      a.ch0 = hf * 128;
+      a.wh = hp.ps_read == 1 ? hp.d_wh_ps[r.in.L & 1] + (int64_t)hf * hp.ps_half_items : hp.d_wh + (int64_t)hf * hp.wh_half_items;
+      a.epi = hp.d_epi + (int64_t)hf * hp.n_epi_rows * 2 * 128;
+    }
+    int64_t code = 0;
+    rc = jg_launch_conv_f16(e, a, s, tapped ? &code : nullptr);
+    if (tapped && (code != 0 || rc != JG_OK)) conv_inst_record(m, i, code);
   }
   return prof_end(e, s, &pe, rc);
 }
