@@ -102,6 +102,20 @@ typedef enum {
                           by 0 where that is 0 (divide_no_nan).  stages: bias / batch norm / unmasked DyT / activation.  C 16, 32
                           or 64, order 1 .. 4, R >= 1: jg_model_create refuses other sizes with the reason; a forward whose rows
                           are longer than R is refused with JG_ERR_UNSUPPORTED before any launch */
+  JG_OP_BILSTM = 17,    /* one MaskedBiLSTM (nnlib/v2/layers.py:1335-1430; Keras 3 Bidirectional(LSTM(U, return_sequences=True),
+                          merge_mode="concat")): in_buf -> out_buf (never the same slot: the rows change width), f32 rows (frames,
+                          L, C) per window in, (frames, L, 2U) out, rows independent.  Per direction, from h = c = 0:
+                          z = x_t W + h R + b; i, f, g, o = sigmoid, sigmoid, tanh, sigmoid of the four U-wide slices of z;
+                          c' = f c + i g; h' = o tanh(c'); the step writes h'.  The backward direction walks t = L - 1 .. 0 and
+                          its outputs stand at their own positions, in channels [U, 2U).  With in_mask a mask slot and arg bit
+                          0 clear, a masked step keeps both states and writes the direction's previous output (zeros while no
+                          valid step has come): x at a masked position reaches no output (a select, never a multiply).
+                          cin = C, cout = 2U, k = U, arg = JG_BILSTM_IGNORE_MASK (1): every step is valid and out_mask =
+                          JG_BUF_NONE; else out_mask = in_mask (a mask slot or none).  f0, stride, dilation unused.  w_off =
+                          per direction (forward, backward) W [C][4U] | R [U][4U] | b [4U], the 4U columns permuted so that
+                          column 64 w + 4 n + g holds gate g (i, f, g, o) of unit 16 w + n.  stages: bias / batch norm /
+                          unmasked DyT / activation, on the 2U output channels.  U 16, 32 or 64, C a multiple of 16 up to
+                          128: jg_model_create refuses other sizes with the reason */
   JG_OP_STRANDS = 10   /* a branched (shared-weight) model over the k strands of a nucleotide input: every strand is a
                           program row of its own (ids (W, k, L), one frame per row); arg = how the strands' predictions
                           merge (jg_merge_kind); the embedding output is their average.  builder.py:1195-1266, :776-791 */
@@ -383,6 +397,11 @@ int jg_lengthattn_chunk(void);
  * partial sum each) - row lengths around them are where a ragged last tile and a second chunk lie */
 int jg_hyena_tile(void);
 int jg_hyena_chunk(void);
+/* the bidirectional LSTM kernel (JG_OP_BILSTM): rows of one workgroup (one 16-row block of the matrix cores; the last
+ * group of a launch is ragged), and time steps whose input projection is formed ahead of the recurrence at a time - row
+ * lengths around the latter are where a ragged last block lies */
+int jg_bilstm_rows(void);
+int jg_bilstm_steps(void);
 
 /* Box calibration (bench.py's `box` object; no counterpart in the reference): about `seconds` (0 < seconds <= 30) of
  * back-to-back launches of a bare v_mfma_f32_32x32x16_f16 loop on random register operands, two waves per SIMD on every

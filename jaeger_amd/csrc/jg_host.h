@@ -14,6 +14,7 @@
 #include "jg_localattn.h"
 #include "jg_lengthattn.h"
 #include "jg_hyena.h"
+#include "jg_bilstm.h"
 
 #pragma GCC visibility push(hidden)
 // ---- shapes: jg_shape_walk (jg_model.hip) is the only place that computes them -------------------------------------
@@ -60,8 +61,9 @@ Place jg_place_op(const jg_model *m, size_t i, const PlaceCtx &c);
 static inline bool jg_place_is_f16(Place p) { return p == PL_RB_CONV1 || p == PL_RB32 || p == PL_RB64 || p == PL_CONV_F16; }
 
 // ---- row mixers ------------------------------------------------------------------------------------------------------
-// The ops that read f32 rows (frames, L, C) from one activation slot and write rows of the same shape to another: packed
-// weights at w_off, an optional mask, bias / batch norm / unmasked DyT / activation stages fused into the store.  What
+// The ops that read f32 rows (frames, L, C) from one activation slot and write rows (frames, L, cout) to another - of the
+// same shape, but for the one kind that widens -: packed weights at w_off, an optional mask, bias / batch norm / unmasked
+// DyT / activation stages fused into the store.  What
 // differs between them is the record below, the per-question switches of jg_model.hip (jg_mixer_*) and the kind-specific
 // lines of launch_mixer (jg_run.hip).
 enum MixerMask {
@@ -76,13 +78,15 @@ struct MixerKind {
   bool six_frames;      // mixes across the six frames of a translated window (else: along each of the id_frames rows)
   bool dilation_1;      // op.dilation must be 1
   bool in_place;        // out_buf may be in_buf
+  bool same_width;      // cout = cin, and f0 is a layer norm's epsilon (else: the kind's own rule, mixer_supports)
   int prof, prof_cvt;   // JG_PROF_* class of the launch and of a layout conversion in front of it (-1: not timed)
 };
 static const MixerKind jg_mixer_kinds[] = {
-    {JG_OP_FRAMEATTN, "frame attention", MM_NONE, true, false, true, JG_PROF_FRAMEATTN, JG_PROF_FRAMEATTN_CVT},
-    {JG_OP_LOCALATTN, "local attention", MM_KEEP, false, true, false, JG_PROF_LOCALATTN, JG_PROF_LOCALATTN_CVT},
-    {JG_OP_LENGTHATTN, "length attention", MM_KEEP_OR_DROP, false, false, false, -1, -1},
-    {JG_OP_HYENA, "hyena", MM_KEEP, false, true, false, -1, -1},
+    {JG_OP_FRAMEATTN, "frame attention", MM_NONE, true, false, true, true, JG_PROF_FRAMEATTN, JG_PROF_FRAMEATTN_CVT},
+    {JG_OP_LOCALATTN, "local attention", MM_KEEP, false, true, false, true, JG_PROF_LOCALATTN, JG_PROF_LOCALATTN_CVT},
+    {JG_OP_LENGTHATTN, "length attention", MM_KEEP_OR_DROP, false, false, false, true, -1, -1},
+    {JG_OP_HYENA, "hyena", MM_KEEP, false, true, false, true, -1, -1},
+    {JG_OP_BILSTM, "bilstm", MM_KEEP_OR_DROP, false, true, false, false, -1, -1},
 };
 static inline const MixerKind *jg_mixer_kind(int kind) {      // nullptr: not a row mixer
   for (const MixerKind &k : jg_mixer_kinds)

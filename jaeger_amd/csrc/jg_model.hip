@@ -22,13 +22,14 @@ static void conv_geometry(int L_in, int k, int stride, int dil, int padding, int
 // ---- row mixers: the questions with kind-specific arithmetic, one switch each (the rest is jg_mixer_kinds) ------------
 // op fields: cin = cout = channels, f0 = the layer norms' epsilon, w_off = the packed weights; the attention ops: k = heads,
 // arg = feed-forward width (frame attention: 0 = no feed-forward half), local attention: stride = half-window; hyena:
-// k = order, arg = flags, stride = rows of the filter table
+// k = order, arg = flags, stride = rows of the filter table; bilstm: cin = C, cout = 2 k, k = units, arg = flags, no epsilon
 static bool mixer_supports(const jg_op &op, char *why, size_t cap) {      // sizes the kernel covers (why: the reason when not)
   switch (op.kind) {
     case JG_OP_FRAMEATTN: return jg_frameattn_supports(op.cin, op.k, op.arg, why, cap);
     case JG_OP_LOCALATTN: return jg_localattn_supports(op.cin, op.k, op.arg, op.stride, why, cap);
     case JG_OP_LENGTHATTN: return jg_lengthattn_supports(op.cin, op.k, op.arg, why, cap);
-    default: return jg_hyena_supports(op.cin, op.k, op.stride, why, cap);
+    case JG_OP_HYENA: return jg_hyena_supports(op.cin, op.k, op.stride, why, cap);
+    default: return jg_bilstm_supports(op.cin, op.k, op.cout, why, cap);
   }
 }
 
@@ -37,7 +38,8 @@ static int64_t mixer_blob_floats(const jg_op &op) {
     case JG_OP_FRAMEATTN: return jg_frameattn_blob_floats(op.cin, op.arg);
     case JG_OP_LOCALATTN: return jg_localattn_blob_floats(op.cin, op.arg);
     case JG_OP_LENGTHATTN: return jg_lengthattn_blob_floats(op.cin, op.arg);
-    default: return jg_hyena_blob_floats(op.cin, op.k, op.stride, op.arg);
+    case JG_OP_HYENA: return jg_hyena_blob_floats(op.cin, op.k, op.stride, op.arg);
+    default: return jg_bilstm_blob_floats(op.cin, op.k);
   }
 }
 
@@ -45,6 +47,7 @@ static int64_t mixer_lds_bytes(const jg_op &op) {      // where the size depends
   switch (op.kind) {
     case JG_OP_LOCALATTN: return jg_localattn_lds_bytes(op.cin, op.cin / op.k, op.stride);
     case JG_OP_LENGTHATTN: return jg_lengthattn_lds_bytes(op.cin, op.k);
+    case JG_OP_BILSTM: return jg_bilstm_lds_bytes(op.cin, op.k);
     default: return 0;
   }
 }
@@ -69,10 +72,12 @@ double jg_mixer_flops(const jg_op &op, const OpShape &r, int nw) {
       const double tiles = (L + JG_LENGTHATTN_TILE - 1) / JG_LENGTHATTN_TILE;
       return (2.0 * (2.0 * C * C + 2.0 * C * op.arg) * L + 2.0 * (2.0 * C * C) * L * tiles + 4.0 * (double)L * L * C) * rows;
     }
-    default: {                 // hyena: the projections and 2 x order x C x L (L + 1) / 2 of the convolutions
+    case JG_OP_HYENA: {        // the projections and 2 x order x C x L (L + 1) / 2 of the convolutions
       const double dense = 2.0 * (op.k + 1 + ((op.arg & JG_HYENA_OUT_PROJ) ? 1 : 0)) * C * C * (double)L;
       return (dense + 2.0 * op.k * C * ((double)L * (L + 1) / 2)) * rows;
     }
+    default:                   // bilstm: x W and h R of the two directions (the element-wise work is not counted)
+      return rows * L * 2.0 * (2.0 * C * 4.0 * op.k + 2.0 * op.k * 4.0 * op.k);
   }
 }
 
@@ -87,6 +92,9 @@ static int mixer_describe(const jg_op &op, size_t i, char *line, size_t cap) {  
     case JG_OP_LENGTHATTN:
       return snprintf(line, cap, "op %zu: length attention c=%d heads=%d key_dim=%d ff=%d %s -> one launch, exact-f32 matrix cores (dense), vector ALUs (scores, context), f32 rows",
                       i, op.cin, op.k, op.cin / op.k, op.arg, op.in_mask >= 0 ? "masked queries and keys" : "no mask");
+    case JG_OP_BILSTM:
+      return snprintf(line, cap, "op %zu: bilstm c=%d units=%d %s -> one launch, %d rows x one direction a workgroup, exact-f32 matrix cores, f32 rows (frames, L, %d)",
+                      i, op.cin, op.k, (op.arg & JG_BILSTM_IGNORE_MASK) ? "mask ignored" : op.in_mask >= 0 ? "masked steps carried" : "no mask", JG_BILSTM_ROWS, op.cout);
     default:
       return snprintf(line, cap, "op %zu: hyena c=%d order=%d table_rows=%d%s%s %s -> %d launches: projections on the exact-f32 matrix cores, causal convolutions on the vector ALUs, f32 rows",
                       i, op.cin, op.k, op.stride, (op.arg & JG_HYENA_OUT_PROJ) ? " output_projection" : "", (op.arg & JG_HYENA_NORMALIZE) ? " filter_normalize" : "",
@@ -97,8 +105,8 @@ static int mixer_describe(const jg_op &op, size_t i, char *line, size_t cap) {  
 static int validate_mixer(const jg_model *m, size_t i) {
   const jg_op &op = m->ops[i];
   const MixerKind &mk = *jg_mixer_kind(op.kind);
-  JG_REQUIRE(op.in_buf >= 0 && op.out_buf >= 0 && op.cin == op.cout && op.f0 > 0.f && (!mk.dilation_1 || op.dilation == 1), JG_ERR_INVALID,
-             "op %zu: a %s op reads and writes an activation slot of cin = cout channels", i, mk.noun);
+  JG_REQUIRE(op.in_buf >= 0 && op.out_buf >= 0 && (!mk.same_width || (op.cin == op.cout && op.f0 > 0.f)) && (!mk.dilation_1 || op.dilation == 1),
+             JG_ERR_INVALID, "op %zu: a %s op reads and writes an activation slot%s", i, mk.noun, mk.same_width ? " of cin = cout channels" : "");
   JG_REQUIRE(mk.in_place || op.in_buf != op.out_buf, JG_ERR_INVALID,
              "op %zu: a %s op cannot run in place (its workgroups read rows that others write)", i, mk.noun);
   const bool mask_slot = op.in_mask >= 0 || op.in_mask == JG_BUF_NONE;
@@ -117,6 +125,11 @@ static int validate_mixer(const jg_model *m, size_t i) {
   }
   if (op.kind == JG_OP_HYENA)
     JG_REQUIRE((op.arg & ~(JG_HYENA_OUT_PROJ | JG_HYENA_NORMALIZE)) == 0, JG_ERR_INVALID, "op %zu: hyena flags %d", i, op.arg);
+  if (op.kind == JG_OP_BILSTM) {
+    JG_REQUIRE((op.arg & ~JG_BILSTM_IGNORE_MASK) == 0, JG_ERR_INVALID, "op %zu: bilstm flags %d", i, op.arg);
+    JG_REQUIRE(op.out_mask == ((op.arg & JG_BILSTM_IGNORE_MASK) ? JG_BUF_NONE : op.in_mask), JG_ERR_INVALID,
+               "op %zu: a bilstm op that ignores the mask leaves none, and one that does not keeps it (out_mask against arg)", i);
+  }
   char why[160];
   JG_REQUIRE(mixer_supports(op, why, sizeof(why)), JG_ERR_UNSUPPORTED, "op %zu: %s with %s", i, mk.noun, why);
   JG_REQUIRE(mixer_lds_bytes(op) <= 160 * 1024, JG_ERR_UNSUPPORTED, "op %zu: %s needs %lld bytes of LDS", i, mk.noun, (long long)mixer_lds_bytes(op));
@@ -139,7 +152,7 @@ static int validate_program(const jg_model *m) {
     auto slot_ok = [](int s, bool allow_ids) {
       return (s >= 0 && s < JG_MAX_BUFS) || s == JG_BUF_NONE || (allow_ids && s == JG_BUF_IDS);
     };
-    JG_REQUIRE(op.kind >= JG_OP_CONV && op.kind <= JG_OP_HYENA, JG_ERR_INVALID,
+    JG_REQUIRE(op.kind >= JG_OP_CONV && op.kind <= JG_OP_BILSTM, JG_ERR_INVALID,
                "op %zu: unknown kind %d", i, op.kind);
     if (op.kind == JG_OP_VECMAX)
       JG_REQUIRE(op.in_vec >= 0 && op.out_vec >= 0 && op.in_vec != op.out_vec && op.k >= 1 && op.cout >= 1 && op.vec_off >= 0,
@@ -309,7 +322,7 @@ int jg_shape_walk(const jg_model *m, int l, std::vector<OpShape> &shp) {
                      "op %zu: hyena over rows of %d positions, the layer's filter table holds %d (seq_len of the layer, or the %d rows a program carries)",
                      i, r.in.L, op.stride, op.stride);
         r.scratch = (int64_t)r.in.frames * mixer_row_scratch(op, r.in.L);
-        r.out = r.in;
+        r.out = Shape{r.in.frames, r.in.L, op.cout};      // (of the same shape, but for the kind that widens)
       } break;
     }
     if (r.out.frames > 0) sh[op.out_buf] = r.out;

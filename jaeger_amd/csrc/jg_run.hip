@@ -506,6 +506,13 @@ static int launch_mixer(jg_model *m, size_t i, const OpShape &r, int nw, hipStre
       a.H = op.k; a.D = op.cin / op.k; a.F = op.arg;
       rc = jg_launch_lengthattn(e, a, s);
     } break;
+    case JG_OP_BILSTM: {
+      JgBilstmArgs a;
+      mixer_args(m, op, r, nw, JG_BILSTM_STEPS, a);
+      a.U = op.k;
+      if (op.arg & JG_BILSTM_IGNORE_MASK) a.mask = nullptr;
+      rc = jg_launch_bilstm(e, a, s);
+    } break;
     default: {      // JG_OP_HYENA
       JgHyenaArgs a;
       mixer_args(m, op, r, nw, JG_HYENA_TILE, a);

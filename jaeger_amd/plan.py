@@ -6,14 +6,15 @@ in ``nnlib/builder.py`` (``build_fragment_classifier`` :442-838,
 :1697-1714).  This module resolves the same section into a flat, fully
 defaulted plan (every default below cites the constructor it comes from) that
 ``program.py`` compiles for the MI355X engine.  Layers outside the conv family
-(multi-scale conv, LSTM, gated pooling ...) raise :class:`UnsupportedLayer`; the attention layers and ``hyena_block``
-are plan nodes of their own.
+(multi-scale conv, gated / last pooling ...) raise :class:`UnsupportedLayer`; the attention layers, ``hyena_block`` and
+``masked_bilstm`` are plan nodes of their own.
 
 Canonical weight names (shared with the loaders in ``weights.py``):
 ``embedding/embeddings``; ``rep/<i>/{kernel,bias,gamma,beta,moving_mean,
 moving_variance,alpha}`` for the i-th ``hidden_layers`` entry;
 ``rep/<i>/block<j>/{conv1,conv2,conv3,bn1,bn2,bn3}/<var>`` inside a
-``residual_block``; ``classifier/<i>/...`` and ``reliability/<i>/...`` for the heads.
+``residual_block``; ``rep/<i>/{forward,backward}/{kernel,recurrent_kernel,bias}`` for a ``masked_bilstm``;
+``classifier/<i>/...`` and ``reliability/<i>/...`` for the heads.
 """
 
 from __future__ import annotations
@@ -250,6 +251,40 @@ def hyena_limit(channels: int, order: int, filter_layers: int, activation) -> st
     if activation is not None and str(activation).lower() not in HYENA_ACTIVATIONS:
         return (f"filter_activation {activation!r} (the host tables the filter with one of "
                 f"{', '.join(HYENA_ACTIVATIONS)} or none)")
+    return None
+
+
+@dataclass
+class BiLstm:
+    """One MaskedBiLSTM (layers.py:1335-1430) on the rows of the (frames, length, channels) tensor: Keras 3
+    ``Bidirectional(LSTM(units, return_sequences=True), merge_mode="concat")`` under the incoming mask - a masked step keeps
+    both states and repeats the direction's previous output (zeros while no valid step has come) - or, with ``ignore_mask``,
+    under none.  ``compute_mask`` returns the mask, or None with ``ignore_mask`` (:1405-1410)."""
+    name: str
+    cin: int
+    units: int
+    ignore_mask: bool = False      # :1361
+
+    @property
+    def channels(self) -> int:
+        """What the layer leaves: the two directions side by side."""
+        return 2 * self.units
+
+
+#: what the kernel (csrc/jg_bilstm.hip) covers
+BILSTM_UNITS = (16, 32, 64)
+BILSTM_MAX_CHANNELS = 128
+# the constructor's own arguments (:1354-1363) plus what keras.layers.Layer.__init__ takes
+_BILSTM_KEYS = {"units", "dropout", "recurrent_dropout", "return_sequences", "use_cudnn", "ignore_mask", "name", "dtype",
+                "trainable"}
+
+
+def bilstm_limit(channels: int, units: int) -> str | None:
+    """Why the bilstm kernel cannot run this layer, or None."""
+    if units not in BILSTM_UNITS:
+        return f"units {units} (the kernel covers {' / '.join(map(str, BILSTM_UNITS))} units)"
+    if channels % 16 or not 16 <= channels <= BILSTM_MAX_CHANNELS:
+        return f"{channels} incoming channels (a multiple of 16 up to {BILSTM_MAX_CHANNELS})"
     return None
 
 
@@ -501,6 +536,26 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
                              None if act is None or str(act).lower() == "linear" else str(act).lower(),
                              bool(cfg.get("filter_normalize", False)), bool(cfg.get("output_projection", False)),
                              None if seq_len is None else int(seq_len)))
+        elif name == "masked_bilstm" and "units" in cfg and not set(cfg) - _BILSTM_KEYS:
+            # builder.py:282, :1155: MaskedBiLSTM(**config); an entry without `units` or with an unknown keyword raises in the
+            # reference's constructor and falls through to the generic refusal below.  dropout / recurrent_dropout matter in
+            # training only, use_cudnn changes no formula
+            if frames is None:
+                raise UnsupportedLayer(f"{p}: masked_bilstm needs the (frames, length, channels) tensor of the "
+                                       "representation learner: not supported in a head or on a strand branch")
+            if not bool(cfg.get("return_sequences", True)):
+                raise UnsupportedLayer(f"{p}: masked_bilstm with return_sequences: false (the tensor loses its length axis, "
+                                       "and no layer behind it here takes a (frames, channels) tensor)")
+            units = int(cfg["units"])
+            why = bilstm_limit(cin, units)
+            if why is not None:
+                raise UnsupportedLayer(f"{p}: masked_bilstm with {why}")
+            nxt = layers[i + 1] if i + 1 < len(layers) else {}
+            if str(nxt.get("name", "")).lower() == "nmd" or (nxt.get("config") or {}).get("return_nmd"):
+                raise UnsupportedLayer(f"{p}: an nmd tap directly behind masked_bilstm is not supported "
+                                       "(the op's store carries no partial sums)")
+            out.append(BiLstm(p, cin, units, bool(cfg.get("ignore_mask", False))))
+            cin = 2 * units
         else:
             raise UnsupportedLayer(
                 f"{p}: layer {name!r} is outside the Conv1D -> norm -> pool -> dense family "
@@ -744,6 +799,8 @@ def weight_shapes(plan: ModelPlan) -> dict[str, tuple]:
                 out.update(length_attn_weight_shapes(layer))
             elif isinstance(layer, Hyena):
                 out.update(hyena_weight_shapes(layer))
+            elif isinstance(layer, BiLstm):
+                out.update(bilstm_weight_shapes(layer))
             elif isinstance(layer, AxialAttn):
                 for j in range(layer.blocks):
                     out.update(length_attn_weight_shapes(layer.length(j)))
@@ -822,6 +879,18 @@ def hyena_weight_shapes(a: Hyena) -> dict[str, tuple]:
     if a.output_projection:
         out[f"{n}/out_proj/kernel"] = (c, c)
         out[f"{n}/out_proj/bias"] = (c,)
+    return out
+
+
+def bilstm_weight_shapes(a: BiLstm) -> dict[str, tuple]:
+    """Keras variable shapes of one MaskedBiLSTM: per direction (``layer.bilstm.forward_layer.cell`` /
+    ``backward_layer.cell``) the LSTMCell's kernel (C, 4U), recurrent_kernel (U, 4U) and bias (4U), the 4U columns in the
+    gate order i, f, g, o."""
+    out: dict[str, tuple] = {}
+    for d in ("forward", "backward"):
+        out[f"{a.name}/{d}/kernel"] = (a.cin, 4 * a.units)
+        out[f"{a.name}/{d}/recurrent_kernel"] = (a.units, 4 * a.units)
+        out[f"{a.name}/{d}/bias"] = (4 * a.units,)
     return out
 
 

@@ -20,6 +20,8 @@ conv launches with epilogue stages:
   (``layers.py:2400-2517``); the mask kept; the norm / activation ride the last block's element-wise op
 * ``hyena_block -> norm -> activation``                       one hyena op (``layers.py:2724-3153``), out of place, the mask
   kept; its implicit filters are tabled here once (:func:`hyena_filter_tables`) and travel in the weight blob
+* ``masked_bilstm -> norm -> activation``                     one bilstm op (``layers.py:1335-1430``), out of place, rows of
+  ``2 * units`` channels; the mask kept, or dropped with ``ignore_mask``
 
 Pure host logic (numpy + ctypes structs): unit-tested on CPU.
 """
@@ -31,7 +33,7 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 from . import _lib as L
-from .plan import HYENA_PE_DIM, Act, AxialAttn, Conv, Dense, FrameAttn, Hyena, LengthAttn, LocalAttn, ModelPlan, Nmd, Norm, ResBlock, UnsupportedLayer, weight_shapes
+from .plan import HYENA_PE_DIM, Act, AxialAttn, BiLstm, Conv, Dense, FrameAttn, Hyena, LengthAttn, LocalAttn, ModelPlan, Nmd, Norm, ResBlock, UnsupportedLayer, weight_shapes
 
 _ACT_CODE = {None: L.ACT_NONE, "linear": L.ACT_NONE, "gelu": L.ACT_GELU_TANH, "gelu_erf": L.ACT_GELU_ERF,
              "relu": L.ACT_RELU, "tanh": L.ACT_TANH, "sigmoid": L.ACT_SIGMOID}
@@ -238,6 +240,20 @@ def pack_hyena(a: Hyena, w: dict[str, np.ndarray]) -> np.ndarray:
     return np.concatenate([np.asarray(x, np.float32).ravel() for x in out])
 
 
+def pack_bilstm(a: BiLstm, w: dict[str, np.ndarray]) -> np.ndarray:
+    """The weights of one MaskedBiLSTM as the kernel reads them (csrc/jg_bilstm.hip): per direction (forward, backward)
+    W [C][4U] | R [U][4U] | b [4U], the 4U columns permuted so that the four gates of one unit stand next to each other and
+    the units of one wave together - column ``64 w + 4 n + g`` holds Keras' column ``g U + 16 w + n`` (gate g of i, f, g, o;
+    unit 16 w + n).  Nothing is folded: the values pass through float64 and are rounded back unchanged."""
+    u = a.units
+    perm = np.arange(4 * u).reshape(4, u).T.ravel()                    # new column 4 unit + g <- old column g U + unit
+    out = []
+    for d in ("forward", "backward"):
+        f64 = lambda name: np.asarray(w[f"{a.name}/{d}/{name}"], np.float64)
+        out += [f64("kernel")[:, perm], f64("recurrent_kernel")[:, perm], f64("bias")[perm]]
+    return np.concatenate([x.ravel() for x in out]).astype(np.float32)
+
+
 @dataclass
 class Program:
     ops: list            # list[L.JgOp]
@@ -266,7 +282,8 @@ class Program:
                         + (f" heads={op.k} ff={op.arg}" if op.kind == L.OP_FRAMEATTN else "")
                         + (f" heads={op.k} ff={op.arg} half_window={op.stride}" if op.kind == L.OP_LOCALATTN else "")
                         + (f" heads={op.k} ff={op.arg}" if op.kind == L.OP_LENGTHATTN else "")
-                        + (f" order={op.k} flags={op.arg} table_rows={op.stride}" if op.kind == L.OP_HYENA else ""))
+                        + (f" order={op.k} flags={op.arg} table_rows={op.stride}" if op.kind == L.OP_HYENA else "")
+                        + (f" units={op.k} ignore_mask={op.arg & L.BILSTM_IGNORE_MASK}" if op.kind == L.OP_BILSTM else ""))
         return rows
 
 
@@ -431,7 +448,7 @@ class _Compiler:
                         w_off=self.blob.add(pack_length_attn(a, self.w)))
 
     def _emit_mixer(self, layers: list, i: int, what: str, buf: int, mask: int, out_mask: int, build_ops: list):
-        """A row-mixer layer (frame / local / length attention, hyena) at ``layers[i]``: its ops - ``build_ops``, one
+        """A row-mixer layer (frame / local / length attention, hyena, bilstm) at ``layers[i]``: its ops - ``build_ops``, one
         ``(in_buf, out_buf) -> op`` per op, each into a fresh slot, never in place - with the bias / batch norm / unmasked
         DyT / activation layers that follow fused into the LAST op's store; a LayerNorm or a masked DyT is cut off into an
         element-wise op behind it.  ``out_mask``: the mask the layers behind see (the incoming one, or none where the layer
@@ -637,6 +654,22 @@ class _Compiler:
                                               cin=layer.channels, cout=layer.channels, stride=hyena_table_rows(layer), f0=HYENA_EPSILON,
                                               arg=(L.HYENA_OUT_PROJ if layer.output_projection else 0) | (L.HYENA_NORMALIZE if layer.filter_normalize else 0),
                                               w_off=self.blob.add(pack_hyena(layer, self.w)))])
+            elif isinstance(layer, BiLstm):
+                # MaskedBiLSTM hands its mask to the two LSTMs (layers.py:1392-1397): a masked step keeps the states and
+                # repeats the previous output, so x at a masked position reaches no output and every output is defined and
+                # finite - the layer may stand behind a local_attention with live dead positions, and its output holds none.
+                # With ignore_mask (or no mask) it reads every position, and drops the mask (:1405-1410)
+                ignore = layer.ignore_mask or mask == L.JG_BUF_NONE
+                if ignore:
+                    self._refuse_unmasked_reader(f"{layer.name}: masked_bilstm with ignore_mask" if layer.ignore_mask
+                                                 else f"{layer.name}: masked_bilstm without a mask")
+                else:
+                    self.dead_margin = None
+                out_mask = L.JG_BUF_NONE if layer.ignore_mask else mask
+                i, buf, mask = self._emit_mixer(layers, i, "masked_bilstm", buf, mask, out_mask, [
+                    lambda src, dst: self._op(L.OP_BILSTM, in_buf=src, out_buf=dst, in_mask=mask, out_mask=out_mask, k=layer.units,
+                                              cin=layer.cin, cout=layer.channels, arg=L.BILSTM_IGNORE_MASK if layer.ignore_mask else 0,
+                                              w_off=self.blob.add(pack_bilstm(layer, self.w)))])
             elif isinstance(layer, LengthAttn):
                 if buf == L.JG_BUF_IDS:
                     raise UnsupportedLayer(f"{layer.name}: transformer_encoder directly on the embedding is not supported")
@@ -698,6 +731,8 @@ class _Compiler:
                 c = layer.filters
             elif isinstance(layer, ResBlock):
                 c = layer.conv2.filters
+            elif isinstance(layer, BiLstm):
+                c = layer.channels
         return c
 
     # ---- heads -----------------------------------------------------------------

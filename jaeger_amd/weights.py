@@ -17,15 +17,24 @@ from pathlib import Path
 
 import numpy as np
 
-from .plan import AxialAttn, Conv, Dense, FrameAttn, Hyena, LengthAttn, LocalAttn, ModelPlan, Nmd, Norm, ResBlock, weight_shapes
+from .plan import AxialAttn, BiLstm, Conv, Dense, FrameAttn, Hyena, LengthAttn, LocalAttn, ModelPlan, Nmd, Norm, ResBlock, weight_shapes
 
 
 def random_weights(plan: ModelPlan, seed: int = 38341) -> dict[str, np.ndarray]:
     rng = np.random.Generator(np.random.PCG64(seed))
     out = {}
-    for name, shp in sorted(weight_shapes(plan).items()):
+    shapes = weight_shapes(plan)
+    for name, shp in sorted(shapes.items()):
         leaf = name.rsplit("/", 1)[1]
-        if leaf == "kernel":
+        if leaf == "recurrent_kernel":
+            # an LSTM's state-to-gates matrix at orthogonal scale (entries of variance 1 / U): the recurrence neither dies
+            # nor saturates, and the gates move
+            lim = math.sqrt(3.0 / shp[0])
+            v = rng.uniform(-lim, lim, shp)
+        elif leaf == "kernel" and f"{name.rsplit('/', 1)[0]}/recurrent_kernel" in shapes:
+            lim = math.sqrt(6.0 / (shp[0] + shp[1] // 4))          # glorot over one gate's (C, U) block
+            v = rng.uniform(-lim, lim, shp)
+        elif leaf == "kernel":
             lim = math.sqrt(6.0 / int(np.prod(shp[:-1])))
             v = rng.uniform(-lim, lim, shp)
         elif leaf == "embeddings":
@@ -36,6 +45,8 @@ def random_weights(plan: ModelPlan, seed: int = 38341) -> dict[str, np.ndarray]:
             v = np.full(shp, 0.5)
         else:  # bias, beta, moving_mean
             v = rng.normal(0.0, 0.1, shp)
+            if f"{name.rsplit('/', 1)[0]}/recurrent_kernel" in shapes:
+                v[shp[0] // 4:shp[0] // 2] += 1.0          # Keras' unit_forget_bias: the forget gate's slice starts at one
         out[name] = v.astype(np.float32)
     # a hyena filter's last Dense at 1/16: its positional rows change slowly, so a He-scaled FFN gives a filter whose lags
     # add up coherently, every convolution multiplies the values by up to the row length, and the logits leave the range in
@@ -61,10 +72,10 @@ def load_npz(path) -> dict[str, np.ndarray]:
 
 
 def attention_layers(plan: ModelPlan) -> list[str]:
-    """Names of the plan's cross_frame_attention, local_attention, transformer_encoder, axial_attention and hyena_block
-    layers: the ones with nested sub-layers, whose weights load from ``.npz`` only."""
+    """Names of the plan's cross_frame_attention, local_attention, transformer_encoder, axial_attention, hyena_block and
+    masked_bilstm layers: the ones with nested sub-layers, whose weights load from ``.npz`` only."""
     return [l.name for seq in (plan.rep, plan.classifier, plan.reliability or []) for l in seq
-            if isinstance(l, (FrameAttn, LocalAttn, LengthAttn, AxialAttn, Hyena))]
+            if isinstance(l, (FrameAttn, LocalAttn, LengthAttn, AxialAttn, Hyena, BiLstm))]
 
 
 def attention_kinds(plan: ModelPlan) -> str:
@@ -72,7 +83,7 @@ def attention_kinds(plan: ModelPlan) -> str:
     layers = [l for seq in (plan.rep, plan.classifier, plan.reliability or []) for l in seq]
     kinds = [name for cls, name in ((FrameAttn, "cross_frame_attention"), (LocalAttn, "local_attention"),
                                           (LengthAttn, "transformer_encoder"), (AxialAttn, "axial_attention"),
-                                          (Hyena, "hyena_block"))
+                                          (Hyena, "hyena_block"), (BiLstm, "masked_bilstm"))
              if any(isinstance(l, cls) for l in layers)]
     return " / ".join(kinds)
 
@@ -83,14 +94,14 @@ NPZ_ROUTE = ("export the model's variables under their canonical names (README: 
 
 def _refuse_attention(plan: ModelPlan, what: str, source) -> None:
     """The Keras-3 ``.weights.h5`` and SavedModel-bundle loaders map weight groups onto plan layers by order and shapes.
-    A MultiHeadAttention nests four EinsumDense sub-layers - and a HyenaBlock an operator, a filter generator and its
-    Sequential filter networks - whose key scheme in either container could only be guessed here (no checkpoint of such
-    a model and no Keras to write one): a guessed scheme would be untestable, so both loaders refuse such a plan and name
-    the route that works."""
+    A MultiHeadAttention nests four EinsumDense sub-layers - a HyenaBlock an operator, a filter generator and its
+    Sequential filter networks, a MaskedBiLSTM a Bidirectional wrapper around two LSTM layers and their cells - whose key
+    scheme in either container could only be guessed here (no checkpoint of such a model and no Keras to write one): a
+    guessed scheme would be untestable, so both loaders refuse such a plan and name the route that works."""
     names = attention_layers(plan)
     if names:
         raise AttentionWeightsUnsupported(
-            f"{source}: the {what} loader does not map the nested sub-layer variables (MultiHeadAttention, HyenaOperator) of "
+            f"{source}: the {what} loader does not map the nested sub-layer variables (MultiHeadAttention, HyenaOperator, Bidirectional) of "
             f"{attention_kinds(plan)} layers ({', '.join(names)}); {NPZ_ROUTE}")
 
 
