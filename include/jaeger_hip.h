@@ -116,7 +116,30 @@ typedef enum {
                           column 64 w + 4 n + g holds gate g (i, f, g, o) of unit 16 w + n.  stages: bias / batch norm /
                           unmasked DyT / activation, on the 2U output channels.  U 16, 32 or 64, C a multiple of 16 up to
                           128: jg_model_create refuses other sizes with the reason */
-  JG_OP_STRANDS = 10   /* a branched (shared-weight) model over the k strands of a nucleotide input: every strand is a
+  JG_OP_MSCONV = 18,    /* one MultiScaleConv1D (nnlib/v2/layers.py:1433-1595): k MaskedConv1Ds (padding same, strides 1) over the
+                          same input, merged along the channels (arg = 0, concat) or summed in branch order (arg = 1, add):
+                          in_buf -> out_buf (never the same slot), f32 rows (frames, L, cin) per window in, (frames, L, cout)
+                          out, rows independent.  Branch b: y_b[t] = act_b(bias_b + sum over its taps j and the channels of
+                          x'[t + j d_b - (k_b - 1) d_b // 2] w_b[j]), x' = x where the in_mask byte is set and the position
+                          lies in the row, zeros elsewhere (in_mask = JG_BUF_NONE: every position of the row).  Every output
+                          position is written.  cin, cout, k = branches, arg = merge kind; f0, stride, dilation unused.
+                          out_mask = the slot a JG_OP_MSMASK wrote, or JG_BUF_NONE - any slot or none, independent of in_mask
+                          (this op reads and writes no mask bytes of it: the field names the mask of its output).  w_off = a
+                          descriptor of 4 x 8 int32 bit patterns - per branch filters, taps, dilation, activation (jg_act),
+                          mask mode, has-bias, channel offset, weight offset (floats from w_off) - then per branch at its weight
+                          offset the kernel [taps][cin][fpad] | bias [fpad], fpad = filters rounded up to 16, padding columns
+                          and an absent bias zeros.  A branch's bias and activation are applied before the sum.  stages: bias
+                          / batch norm / unmasked DyT / activation, on the cout output channels.  cin and cout a multiple of 16
+                          up to 128, 1 - 4 branches, filters a multiple of 8 up to 128, taps 1 - 15, (taps - 1) x dilation up to
+                          64; every offset inside the blob; concat: the channel offsets tile [0, cout) in branch order, add:
+                          every branch has cout filters: jg_model_create refuses anything else with the reason */
+  JG_OP_MSMASK = 19,    /* the output mask of a MultiScaleConv1D - what JG_OP_MASK is to JG_OP_CONV: in_mask (a mask slot) ->
+                          out_mask (another mask slot), out[t] = AND over the k branches of the branch's rule - any: c > 0,
+                          majority: c >= (taps + 1) / 2 of the full taps, at the row ends too, strict: c == taps - on the
+                          count c of set in_mask bytes among the positions t + j d - (taps - 1) d // 2 inside the row
+                          (layers.py:1237-1254, :1544-1548).  cin, cout, k, arg and w_off as in the JG_OP_MSCONV it belongs
+                          to (the same descriptor, validated the same way); no activation slot is read or written */
+  JG_OP_STRANDS = 10  /* a branched (shared-weight) model over the k strands of a nucleotide input: every strand is a
                           program row of its own (ids (W, k, L), one frame per row); arg = how the strands' predictions
                           merge (jg_merge_kind); the embedding output is their average.  builder.py:1195-1266, :776-791 */
 } jg_op_kind;
@@ -402,6 +425,9 @@ int jg_hyena_chunk(void);
  * lengths around the latter are where a ragged last block lies */
 int jg_bilstm_rows(void);
 int jg_bilstm_steps(void);
+/* the multi-scale conv kernel (JG_OP_MSCONV): consecutive positions of one row a workgroup owns - row lengths around its
+ * multiples are where a ragged last tile and a halo across a tile border lie */
+int jg_msconv_tile(void);
 
 /* Box calibration (bench.py's `box` object; no counterpart in the reference): about `seconds` (0 < seconds <= 30) of
  * back-to-back launches of a bare v_mfma_f32_32x32x16_f16 loop on random register operands, two waves per SIMD on every

@@ -40,7 +40,7 @@ JG_PROF_MFMA_F16X3, JG_PROF_MFMA_F32, JG_PROF_TABLE, JG_PROF_FUSED_SMALL, JG_PRO
 TAP_F16S, TAP_PHASE_SPLIT, TAP_WINDOW_PACKED, TAP_TABLE_LOOKUP, TAP_NARROW, TAP_EXACT_F32, TAP_FUSED_RESBLOCK = 1, 2, 4, 8, 16, 32, 64
 
 # jg_op_kind
-OP_CONV, OP_MASK, OP_POOL, OP_DENSE, OP_ELTWISE, OP_NMD_FINAL, OP_OODSIG, OP_MAXPOOL1D, OP_FRAMESUM, OP_STRANDS, OP_EMBED, OP_VECMAX, OP_FRAMEATTN, OP_LOCALATTN, OP_LENGTHATTN, OP_HYENA, OP_BILSTM = range(1, 18)
+OP_CONV, OP_MASK, OP_POOL, OP_DENSE, OP_ELTWISE, OP_NMD_FINAL, OP_OODSIG, OP_MAXPOOL1D, OP_FRAMESUM, OP_STRANDS, OP_EMBED, OP_VECMAX, OP_FRAMEATTN, OP_LOCALATTN, OP_LENGTHATTN, OP_HYENA, OP_BILSTM, OP_MSCONV, OP_MSMASK = range(1, 20)
 LOCALATTN_TILE = 80          # jg_localattn_tile(): query positions of one work item of the local-attention kernel
 LOCALATTN_MAX_HALF = 32
 LENGTHATTN_TILE, LENGTHATTN_CHUNK = 128, 64      # jg_lengthattn_tile(), jg_lengthattn_chunk()
@@ -49,6 +49,9 @@ HYENA_OUT_PROJ, HYENA_NORMALIZE = 1, 2           # JG_OP_HYENA's arg bits
 HYENA_MAX_ORDER = 4
 BILSTM_ROWS, BILSTM_STEPS = 16, 8                 # jg_bilstm_rows(), jg_bilstm_steps()
 BILSTM_IGNORE_MASK = 1                           # JG_OP_BILSTM's arg bit
+MSCONV_TILE = 64                                 # jg_msconv_tile(): positions of one row a workgroup of the multi-scale conv kernel owns
+MSCONV_CONCAT, MSCONV_ADD = 0, 1                 # JG_OP_MSCONV's arg: the merge kind
+MSCONV_MAX_BRANCHES, MSCONV_DESC_FIELDS = 4, 8   # the descriptor at the head of the op's blob: 4 x 8 int32 bit patterns
 # jg_stage_kind
 ST_NONE, ST_BIAS, ST_BN, ST_DYT, ST_ADD, ST_ACT, ST_NMD, ST_MASKMUL, ST_LN = range(9)
 # jg_act
@@ -137,6 +140,7 @@ SYMBOLS = {
     "jg_hyena_chunk": (C.c_int, []),
     "jg_bilstm_rows": (C.c_int, []),
     "jg_bilstm_steps": (C.c_int, []),
+    "jg_msconv_tile": (C.c_int, []),
     "jg_box_calibrate": (C.c_int, [_vp, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),
     "jg_terminal_repeats": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int32, _vp]),
     "jg_viterbi_decode": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int64, _vp, _vp]),

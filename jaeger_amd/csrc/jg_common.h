@@ -328,6 +328,10 @@ struct ConvHPrep {          // per CONV op: split-f16 operands (built at model c
   unsigned ep = JG_EP_GENERIC;
   float alpha1 = 0.f, alpha2 = 0.f;
   int dytmask1 = 0, dytmask2 = 0;
+  // (MSCONV ops) from the descriptor jg_model_create validated: the largest left / right reach over the branches, and the
+  // sum over the branches of taps x filters (the FLOP count)
+  int ms_halo_l = 0, ms_halo_r = 0;
+  int64_t ms_macs = 0;
 };
 
 struct JgSmallNet;

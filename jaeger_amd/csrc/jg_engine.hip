@@ -23,6 +23,7 @@ extern "C" int jg_hyena_tile(void) { return JG_HYENA_TILE; }
 extern "C" int jg_hyena_chunk(void) { return JG_HYENA_CHUNK; }
 extern "C" int jg_bilstm_rows(void) { return JG_BILSTM_ROWS; }
 extern "C" int jg_bilstm_steps(void) { return JG_BILSTM_STEPS; }
+extern "C" int jg_msconv_tile(void) { return JG_MSCONV_TILE; }
 extern "C" int jg_sizeof(int which) {
   return which == 0 ? (int)sizeof(jg_op) : (which == 1 ? (int)sizeof(jg_stage) : -1);
 }

@@ -15,6 +15,7 @@
 #include "jg_lengthattn.h"
 #include "jg_hyena.h"
 #include "jg_bilstm.h"
+#include "jg_msconv.h"
 
 #pragma GCC visibility push(hidden)
 // ---- shapes: jg_shape_walk (jg_model.hip) is the only place that computes them -------------------------------------
@@ -62,7 +63,7 @@ static inline bool jg_place_is_f16(Place p) { return p == PL_RB_CONV1 || p == PL
 
 // ---- row mixers ------------------------------------------------------------------------------------------------------
 // The ops that read f32 rows (frames, L, C) from one activation slot and write rows (frames, L, cout) to another - of the
-// same shape, but for the one kind that widens -: packed weights at w_off, an optional mask, bias / batch norm / unmasked
+// same shape, but for the kinds that change the width -: packed weights at w_off, an optional mask, bias / batch norm / unmasked
 // DyT / activation stages fused into the store.  What
 // differs between them is the record below, the per-question switches of jg_model.hip (jg_mixer_*) and the kind-specific
 // lines of launch_mixer (jg_run.hip).
@@ -70,6 +71,8 @@ enum MixerMask {
   MM_NONE,          // out_mask = none
   MM_KEEP,          // out_mask = in_mask (a mask slot or none)
   MM_KEEP_OR_DROP,  // out_mask = in_mask or none
+  MM_OWN,           // out_mask = any mask slot or none, independent of in_mask (a mask slot or none): a mask op of the layer's
+                    // own wrote it
 };
 struct MixerKind {
   int kind;
@@ -87,6 +90,7 @@ static const MixerKind jg_mixer_kinds[] = {
     {JG_OP_LENGTHATTN, "length attention", MM_KEEP_OR_DROP, false, false, false, true, -1, -1},
     {JG_OP_HYENA, "hyena", MM_KEEP, false, true, false, true, -1, -1},
     {JG_OP_BILSTM, "bilstm", MM_KEEP_OR_DROP, false, true, false, false, -1, -1},
+    {JG_OP_MSCONV, "multi-scale conv", MM_OWN, false, true, false, false, -1, -1},
 };
 static inline const MixerKind *jg_mixer_kind(int kind) {      // nullptr: not a row mixer
   for (const MixerKind &k : jg_mixer_kinds)
@@ -94,8 +98,8 @@ static inline const MixerKind *jg_mixer_kind(int kind) {      // nullptr: not a 
   return nullptr;
 }
 static inline bool jg_op_is_mixer(int kind) { return jg_mixer_kind(kind) != nullptr; }
-// FLOPs of op (a row mixer) over nw windows of the rows r records (jg_model.hip): the model's FLOPs and the profiling bracket
-double jg_mixer_flops(const jg_op &op, const OpShape &r, int nw);
+// FLOPs of op i (a row mixer) over nw windows of the rows r records (jg_model.hip): the model's FLOPs and the profiling bracket
+double jg_mixer_flops(const jg_model *m, size_t i, const OpShape &r, int nw);
 
 // does op read / write activation slot `buf` as a tensor (jg_prepare.hip; NMD_FINAL counts as a reader: it takes the
 // slot's shape)

@@ -22,9 +22,11 @@ static void conv_geometry(int L_in, int k, int stride, int dil, int padding, int
 // ---- row mixers: the questions with kind-specific arithmetic, one switch each (the rest is jg_mixer_kinds) ------------
 // op fields: cin = cout = channels, f0 = the layer norms' epsilon, w_off = the packed weights; the attention ops: k = heads,
 // arg = feed-forward width (frame attention: 0 = no feed-forward half), local attention: stride = half-window; hyena:
-// k = order, arg = flags, stride = rows of the filter table; bilstm: cin = C, cout = 2 k, k = units, arg = flags, no epsilon
+// k = order, arg = flags, stride = rows of the filter table; bilstm: cin = C, cout = 2 k, k = units, arg = flags, no epsilon;
+// multi-scale conv: cin, cout, k = branches, arg = merge kind, no epsilon - the rest in the descriptor at w_off (msconv_desc)
 static bool mixer_supports(const jg_op &op, char *why, size_t cap) {      // sizes the kernel covers (why: the reason when not)
   switch (op.kind) {
+    case JG_OP_MSCONV: return jg_msconv_supports(op.cin, op.k, op.cout, op.arg, why, cap);
     case JG_OP_FRAMEATTN: return jg_frameattn_supports(op.cin, op.k, op.arg, why, cap);
     case JG_OP_LOCALATTN: return jg_localattn_supports(op.cin, op.k, op.arg, op.stride, why, cap);
     case JG_OP_LENGTHATTN: return jg_lengthattn_supports(op.cin, op.k, op.arg, why, cap);
@@ -33,8 +35,19 @@ static bool mixer_supports(const jg_op &op, char *why, size_t cap) {      // siz
   }
 }
 
-static int64_t mixer_blob_floats(const jg_op &op) {
+// the descriptor of a multi-scale conv op or of its mask op out of the host blob jg_model_create was given, validated
+static int msconv_desc(const jg_model *m, size_t i, const float *weights, JgMsconvDesc *d) {
+  const jg_op &op = m->ops[i];
+  JG_REQUIRE(op.w_off >= 0 && op.w_off < m->n_w, JG_ERR_INVALID, "op %zu: multi-scale conv descriptor outside the weight blob", i);
+  char why[200];
+  const int rc = jg_msconv_read_desc(weights + op.w_off, m->n_w - op.w_off, op.cin, op.k, op.cout, op.arg, d, why, sizeof(why));
+  if (rc != JG_OK) jg_set_error("op %zu: multi-scale conv with %s", i, why);
+  return rc;
+}
+
+static int64_t mixer_blob_floats(const jg_op &op) {      // (multi-scale conv: the descriptor; msconv_desc checks what it names)
   switch (op.kind) {
+    case JG_OP_MSCONV: return JG_MSCONV_DESC_FLOATS;
     case JG_OP_FRAMEATTN: return jg_frameattn_blob_floats(op.cin, op.arg);
     case JG_OP_LOCALATTN: return jg_localattn_blob_floats(op.cin, op.arg);
     case JG_OP_LENGTHATTN: return jg_lengthattn_blob_floats(op.cin, op.arg);
@@ -56,7 +69,8 @@ static int64_t mixer_row_scratch(const jg_op &op, int L) {      // floats of scr
   return op.kind == JG_OP_HYENA ? jg_hyena_row_scratch(op.cin, op.k, L) : 0;
 }
 
-double jg_mixer_flops(const jg_op &op, const OpShape &r, int nw) {
+double jg_mixer_flops(const jg_model *m, size_t i, const OpShape &r, int nw) {
+  const jg_op &op = m->ops[i];
   const int C = op.cin, L = r.in.L;
   const double rows = (double)(nw * r.in.frames);
   switch (op.kind) {
@@ -76,6 +90,8 @@ double jg_mixer_flops(const jg_op &op, const OpShape &r, int nw) {
       const double dense = 2.0 * (op.k + 1 + ((op.arg & JG_HYENA_OUT_PROJ) ? 1 : 0)) * C * C * (double)L;
       return (dense + 2.0 * op.k * C * ((double)L * (L + 1) / 2)) * rows;
     }
+    case JG_OP_MSCONV:         // per position and branch taps x cin x filters multiply-adds (the padded columns are not counted)
+      return rows * L * 2.0 * C * (double)m->hprep[i].ms_macs;
     default:                   // bilstm: x W and h R of the two directions (the element-wise work is not counted)
       return rows * L * 2.0 * (2.0 * C * 4.0 * op.k + 2.0 * op.k * 4.0 * op.k);
   }
@@ -92,6 +108,9 @@ static int mixer_describe(const jg_op &op, size_t i, char *line, size_t cap) {  
     case JG_OP_LENGTHATTN:
       return snprintf(line, cap, "op %zu: length attention c=%d heads=%d key_dim=%d ff=%d %s -> one launch, exact-f32 matrix cores (dense), vector ALUs (scores, context), f32 rows",
                       i, op.cin, op.k, op.cin / op.k, op.arg, op.in_mask >= 0 ? "masked queries and keys" : "no mask");
+    case JG_OP_MSCONV:
+      return snprintf(line, cap, "op %zu: multi-scale conv cin=%d branches=%d merge=%s cout=%d %s -> one launch, %d positions a workgroup, the input tile read once, exact-f32 matrix cores, f32 rows (frames, L, %d)",
+                      i, op.cin, op.k, op.arg == JG_MSCONV_ADD ? "add" : "concat", op.cout, op.in_mask >= 0 ? "masked input" : "no mask", JG_MSCONV_TILE, op.cout);
     case JG_OP_BILSTM:
       return snprintf(line, cap, "op %zu: bilstm c=%d units=%d %s -> one launch, %d rows x one direction a workgroup, exact-f32 matrix cores, f32 rows (frames, L, %d)",
                       i, op.cin, op.k, (op.arg & JG_BILSTM_IGNORE_MASK) ? "mask ignored" : op.in_mask >= 0 ? "masked steps carried" : "no mask", JG_BILSTM_ROWS, op.cout);
@@ -102,7 +121,7 @@ static int mixer_describe(const jg_op &op, size_t i, char *line, size_t cap) {  
   }
 }
 
-static int validate_mixer(const jg_model *m, size_t i) {
+static int validate_mixer(const jg_model *m, size_t i, const float *weights) {
   const jg_op &op = m->ops[i];
   const MixerKind &mk = *jg_mixer_kind(op.kind);
   JG_REQUIRE(op.in_buf >= 0 && op.out_buf >= 0 && (!mk.same_width || (op.cin == op.cout && op.f0 > 0.f)) && (!mk.dilation_1 || op.dilation == 1),
@@ -122,6 +141,10 @@ static int validate_mixer(const jg_model *m, size_t i) {
       JG_REQUIRE(mask_slot && (op.out_mask == op.in_mask || op.out_mask == JG_BUF_NONE), JG_ERR_INVALID,
                  "op %zu: a %s op keeps its mask or drops it (out_mask = in_mask or none)", i, mk.noun);
       break;
+    case MM_OWN:
+      JG_REQUIRE(mask_slot && (op.out_mask >= 0 || op.out_mask == JG_BUF_NONE), JG_ERR_INVALID,
+                 "op %zu: a %s op reads a mask slot or none and names the mask slot of its output or none", i, mk.noun);
+      break;
   }
   if (op.kind == JG_OP_HYENA)
     JG_REQUIRE((op.arg & ~(JG_HYENA_OUT_PROJ | JG_HYENA_NORMALIZE)) == 0, JG_ERR_INVALID, "op %zu: hyena flags %d", i, op.arg);
@@ -137,6 +160,13 @@ static int validate_mixer(const jg_model *m, size_t i) {
              "op %zu: %s needs the frame rows of a translated window (not a strand program)", i, mk.noun);
   JG_REQUIRE(op.w_off >= 0 && op.w_off + mixer_blob_floats(op) <= m->n_w, JG_ERR_INVALID,
              "op %zu: %s weights outside the weight blob", i, mk.noun);
+  if (op.kind == JG_OP_MSCONV) {
+    JgMsconvDesc d;
+    const int rc = msconv_desc(m, i, weights, &d);
+    if (rc != JG_OK) return rc;
+    const int64_t lds = jg_msconv_lds_bytes(op.cin, op.cout, d.halo_l, d.halo_r);
+    JG_REQUIRE(lds <= 160 * 1024, JG_ERR_UNSUPPORTED, "op %zu: %s needs %lld bytes of LDS", i, mk.noun, (long long)lds);
+  }
   for (int s = 0; s < op.n_stages; ++s) {
     const int kd = op.stages[s].kind;
     JG_REQUIRE(kd == JG_ST_BIAS || kd == JG_ST_BN || kd == JG_ST_ACT || (kd == JG_ST_DYT && op.stages[s].arg == 0), JG_ERR_UNSUPPORTED,
@@ -145,14 +175,14 @@ static int validate_mixer(const jg_model *m, size_t i) {
   return JG_OK;
 }
 
-static int validate_program(const jg_model *m) {
+static int validate_program(const jg_model *m, const float *weights) {
   int rc;
   for (size_t i = 0; i < m->ops.size(); ++i) {
     const jg_op &op = m->ops[i];
     auto slot_ok = [](int s, bool allow_ids) {
       return (s >= 0 && s < JG_MAX_BUFS) || s == JG_BUF_NONE || (allow_ids && s == JG_BUF_IDS);
     };
-    JG_REQUIRE(op.kind >= JG_OP_CONV && op.kind <= JG_OP_BILSTM, JG_ERR_INVALID,
+    JG_REQUIRE(op.kind >= JG_OP_CONV && op.kind <= JG_OP_MSMASK, JG_ERR_INVALID,
                "op %zu: unknown kind %d", i, op.kind);
     if (op.kind == JG_OP_VECMAX)
       JG_REQUIRE(op.in_vec >= 0 && op.out_vec >= 0 && op.in_vec != op.out_vec && op.k >= 1 && op.cout >= 1 && op.vec_off >= 0,
@@ -190,7 +220,13 @@ static int validate_program(const jg_model *m) {
       JG_REQUIRE(op.in_buf != JG_BUF_IDS && op.in_mask != JG_BUF_IDS, JG_ERR_INVALID,
                  "op %zu: reads the id tensor directly in a program that opens with an embedding op (its buffer and mask take the tensor's place)", i);
     }
-    if (jg_op_is_mixer(op.kind) && (rc = validate_mixer(m, i)) != JG_OK) return rc;
+    if (jg_op_is_mixer(op.kind) && (rc = validate_mixer(m, i, weights)) != JG_OK) return rc;
+    if (op.kind == JG_OP_MSMASK) {
+      JG_REQUIRE(op.in_mask >= 0 && op.out_mask >= 0 && op.in_mask != op.out_mask, JG_ERR_INVALID,
+                 "op %zu: a multi-scale mask op reads one mask slot and writes another", i);
+      JgMsconvDesc d;
+      if ((rc = msconv_desc(m, i, weights, &d)) != JG_OK) return rc;
+    }
     if (op.kind == JG_OP_DENSE) {
       JG_REQUIRE(off_ok(op.w_off, (int64_t)op.cin * op.cout), JG_ERR_INVALID,
                  "op %zu: dense kernel outside the weight blob", i);
@@ -275,6 +311,11 @@ int jg_shape_walk(const jg_model *m, int l, std::vector<OpShape> &shp) {
         JG_REQUIRE(op.out_mask >= 0 && r.L_out > 0, JG_ERR_INVALID, "op %zu: bad mask op", i);
         r.m_out = r.L_out;
         break;
+      case JG_OP_MSMASK:
+        r.m_in = mL[op.in_mask];
+        JG_REQUIRE(r.m_in > 0, JG_ERR_INVALID, "op %zu: a multi-scale mask op on a mask slot nothing has written", i);
+        r.L_out = r.m_out = r.m_in;      // padding same, strides 1
+        break;
       case JG_OP_ELTWISE:
         JG_REQUIRE(r.in.C == op.cout, JG_ERR_INVALID, "op %zu: eltwise channel mismatch", i);
         r.out = r.in;
@@ -317,6 +358,9 @@ int jg_shape_walk(const jg_model *m, int l, std::vector<OpShape> &shp) {
           r.m_in = mL[op.in_mask];
           JG_REQUIRE(r.m_in == r.in.L, JG_ERR_INVALID, "op %zu: %s over rows of %d positions with a mask of %d", i, mk.noun, r.in.L, r.m_in);
         }
+        if (mk.mask == MM_OWN && op.out_mask >= 0)
+          JG_REQUIRE(mL[op.out_mask] == r.in.L, JG_ERR_INVALID, "op %zu: %s over rows of %d positions names an output mask of %d", i, mk.noun,
+                     r.in.L, mL[op.out_mask]);
         if (op.kind == JG_OP_HYENA)
           JG_REQUIRE(r.in.L <= op.stride, JG_ERR_UNSUPPORTED,
                      "op %zu: hyena over rows of %d positions, the layer's filter table holds %d (seq_len of the layer, or the %d rows a program carries)",
@@ -343,7 +387,7 @@ static void fold_shapes(const jg_model *m, int l, const std::vector<OpShape> &sh
     const jg_op &op = m->ops[i];
     const OpShape &r = shp[i];
     if (op.kind == JG_OP_CONV) fl += 2.0 * op.k * op.cin * op.cout * (double)r.in.frames * r.L_out;
-    if (jg_op_is_mixer(op.kind)) fl += jg_mixer_flops(op, r, 1);
+    if (jg_op_is_mixer(op.kind)) fl += jg_mixer_flops(m, i, r, 1);
     if (r.m_out > 0) msk_elems[op.out_mask] = std::max<int64_t>(msk_elems[op.out_mask], (int64_t)m->id_frames * r.m_out);
     if (r.vec_need > 0) vec_w[op.out_vec] = std::max(vec_w[op.out_vec], r.vec_need);
     if (r.out.frames == 0 || (tab && (int)i == m->tab_conv)) continue;      // (table net: the activation never exists)
@@ -457,7 +501,7 @@ extern "C" int jg_model_create(jg_engine *e, const jg_op *ops, int n_ops, const 
   m->ops.assign(ops, ops + n_ops);
   m->n_w = n_weights;
   m->vocab = vocab;
-  int rc = validate_program(m);
+  int rc = validate_program(m, weights);
   if (rc != JG_OK) { delete m; return rc; }
   if (m->ops[0].kind == JG_OP_EMBED && m->vocab > 256) m->id_bytes = 2;
   if (m->ops.back().kind == JG_OP_STRANDS) {
@@ -479,6 +523,12 @@ extern "C" int jg_model_create(jg_engine *e, const jg_op *ops, int n_ops, const 
   if (rc != JG_OK) { jg_model_destroy(m); return rc; }
   rc = jg_prepare_f16(m, weights);
   if (rc != JG_OK) { jg_model_destroy(m); return rc; }
+  for (size_t i = 0; i < m->ops.size(); ++i) {      // (behind jg_prepare_f16: it sizes the per-op records)
+    JgMsconvDesc d;
+    if (m->ops[i].kind != JG_OP_MSCONV) continue;
+    if ((rc = msconv_desc(m, i, weights, &d)) != JG_OK) { jg_model_destroy(m); return rc; }
+    m->hprep[i].ms_halo_l = d.halo_l; m->hprep[i].ms_halo_r = d.halo_r; m->hprep[i].ms_macs = d.macs;
+  }
   rc = jg_plan_phase_split(m, weights);
   if (rc != JG_OK) { jg_model_destroy(m); return rc; }
   rc = jg_plan_resblocks(m, weights);
@@ -619,7 +669,7 @@ int jg_ensure_workspace(jg_model *m, int64_t chunk, int l, const std::vector<OpS
 // why op i's output is never stored under placement c (rows of l positions when c has a row length), or nullptr
 const char *jg_tap_refusal(const jg_model *m, size_t i, const PlaceCtx &c, int l, char *why, size_t cap) {
   const jg_op &op = m->ops[i];
-  if (op.kind != JG_OP_CONV && op.kind != JG_OP_MASK && op.kind != JG_OP_ELTWISE && op.kind != JG_OP_EMBED &&
+  if (op.kind != JG_OP_CONV && op.kind != JG_OP_MASK && op.kind != JG_OP_MSMASK && op.kind != JG_OP_ELTWISE && op.kind != JG_OP_EMBED &&
       op.kind != JG_OP_MAXPOOL1D && op.kind != JG_OP_FRAMESUM && !jg_op_is_mixer(op.kind)) {
     snprintf(why, cap, "op %zu (kind %d) writes a vector or nothing - pool, dense and vector results are outputs already", i, op.kind);
     return why;
@@ -649,7 +699,7 @@ const char *jg_tap_refusal(const jg_model *m, size_t i, const PlaceCtx &c, int l
 int jg_tap_copy(jg_model *m, size_t i, const OpShape &r, const PlaceCtx &c, int nw, hipStream_t s) {
   const jg_op &op = m->ops[i];
   uint8_t *dst = static_cast<uint8_t *>(m->tap_dst);
-  if (op.kind == JG_OP_MASK) {
+  if (op.kind == JG_OP_MASK || op.kind == JG_OP_MSMASK) {
     const int64_t per_row = (int64_t)m->id_frames * r.m_out;         // frames x L_out bytes per program row
     JG_REQUIRE((m->tap_row0 + nw) * per_row <= m->tap_bytes, JG_ERR_INVALID, "tap: destination of %lld bytes too small",
                (long long)m->tap_bytes);
@@ -715,7 +765,7 @@ extern "C" int jg_model_tap_shape(const jg_model *m, int op, int32_t l, int64_t 
   if (rc != JG_OK) return rc;
   const OpShape &r = shp[(size_t)op];                   // the tensor this op wrote, per window
   shape[0] = m->strands;
-  if (m->ops[(size_t)op].kind == JG_OP_MASK) {
+  if (m->ops[(size_t)op].kind == JG_OP_MASK || m->ops[(size_t)op].kind == JG_OP_MSMASK) {
     shape[1] = m->id_frames; shape[2] = r.m_out; shape[3] = 1;
   } else {
     shape[1] = r.out.frames; shape[2] = r.out.L; shape[3] = r.out.C;

@@ -749,7 +749,7 @@ int jg_plan_phase_split(jg_model *m, const float *weights) {
         if (!conv_reader || adds_it || cvt_here || mask_rewritten) ok = false;
         else readers.push_back(j);
       }
-      if (o.kind == JG_OP_MASK && po.out_mask >= 0 && o.out_mask == po.out_mask) mask_rewritten = true;
+      if ((o.kind == JG_OP_MASK || o.kind == JG_OP_MSMASK) && po.out_mask >= 0 && o.out_mask == po.out_mask) mask_rewritten = true;
       if (jg_op_writes(m->ops[j], po.out_buf)) break;
     }
     if (!ok || readers.empty()) continue;

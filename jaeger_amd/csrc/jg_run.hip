@@ -484,7 +484,7 @@ static int launch_mixer(jg_model *m, size_t i, const OpShape &r, int nw, hipStre
   const int64_t scratch = (int64_t)nw * r.scratch * (int64_t)sizeof(float);
   JG_REQUIRE(scratch <= m->hy_cap, JG_ERR_INVALID, "op %zu: hyena scratch of %lld bytes, %lld needed", i, (long long)m->hy_cap, (long long)scratch);
   ProfEvent pe;
-  int rc = prof >= 0 ? prof_begin(e, s, prof, jg_mixer_flops(op, r, nw), &pe) : JG_OK;
+  int rc = prof >= 0 ? prof_begin(e, s, prof, jg_mixer_flops(m, i, r, nw), &pe) : JG_OK;
   if (rc != JG_OK) return rc;
   switch (op.kind) {
     case JG_OP_FRAMEATTN: {
@@ -512,6 +512,13 @@ static int launch_mixer(jg_model *m, size_t i, const OpShape &r, int nw, hipStre
       a.U = op.k;
       if (op.arg & JG_BILSTM_IGNORE_MASK) a.mask = nullptr;
       rc = jg_launch_bilstm(e, a, s);
+    } break;
+    case JG_OP_MSCONV: {
+      JgMsconvArgs a;
+      mixer_args(m, op, r, nw, JG_MSCONV_TILE, a);
+      a.cout = op.cout; a.n_branches = op.k; a.merge = op.arg;
+      a.halo_l = m->hprep[i].ms_halo_l; a.halo_r = m->hprep[i].ms_halo_r;
+      rc = jg_launch_msconv(e, a, s);
     } break;
     default: {      // JG_OP_HYENA
       JgHyenaArgs a;
@@ -551,6 +558,8 @@ static int launch_ordinary(jg_model *m, size_t i, const OpShape &r, const uint8_
     case JG_OP_MASK:
       return jg_launch_mask(op.in_mask == JG_BUF_IDS ? d_ids : m->msk[op.in_mask], nw * m->id_frames, r.m_in, r.L_out, op.k, op.stride,
                             op.dilation, r.pad_left, op.mask_mode, m->msk[op.out_mask], s);
+    case JG_OP_MSMASK:
+      return jg_launch_msmask(m->msk[op.in_mask], nw * m->id_frames, r.m_in, m->d_w + op.w_off, op.k, m->msk[op.out_mask], s);
     case JG_OP_ELTWISE: return launch_eltwise(m, i, r, nw, s);
     case JG_OP_MAXPOOL1D:
       if (m->precision == 1 && m->hprep[i].pool_f16s)

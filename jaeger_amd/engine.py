@@ -326,7 +326,7 @@ class HipModel:
         shape = (C.c_int64 * 4)()
         L.check(self.lib.jg_model_tap_shape(self.handle, int(op), ids.shape[2], shape), "jg_model_tap_shape")
         rows, frames, l_out, c = (int(v) for v in shape)
-        is_mask = self.program.ops[op].kind == L.OP_MASK
+        is_mask = self.program.ops[op].kind in (L.OP_MASK, L.OP_MSMASK)
         out = np.zeros((ids.shape[0] * rows, frames, l_out) if is_mask else (ids.shape[0] * rows, frames, l_out, c),
                        np.uint8 if is_mask else np.float32)
         L.check(self.lib.jg_model_set_tap(self.handle, int(op), _ptr(out), out.nbytes), "jg_model_set_tap")

@@ -6,14 +6,15 @@ in ``nnlib/builder.py`` (``build_fragment_classifier`` :442-838,
 :1697-1714).  This module resolves the same section into a flat, fully
 defaulted plan (every default below cites the constructor it comes from) that
 ``program.py`` compiles for the MI355X engine.  Layers outside the conv family
-(multi-scale conv, gated / last pooling ...) raise :class:`UnsupportedLayer`; the attention layers, ``hyena_block`` and
-``masked_bilstm`` are plan nodes of their own.
+(gated / last pooling, parallel branches ...) raise :class:`UnsupportedLayer`; the attention layers, ``hyena_block``,
+``masked_bilstm`` and ``multi_scale_conv`` are plan nodes of their own.
 
 Canonical weight names (shared with the loaders in ``weights.py``):
 ``embedding/embeddings``; ``rep/<i>/{kernel,bias,gamma,beta,moving_mean,
 moving_variance,alpha}`` for the i-th ``hidden_layers`` entry;
 ``rep/<i>/block<j>/{conv1,conv2,conv3,bn1,bn2,bn3}/<var>`` inside a
 ``residual_block``; ``rep/<i>/{forward,backward}/{kernel,recurrent_kernel,bias}`` for a ``masked_bilstm``;
+``rep/<i>/branch<b>/{kernel,bias}`` for the b-th branch of a ``multi_scale_conv``;
 ``classifier/<i>/...`` and ``reliability/<i>/...`` for the heads.
 """
 
@@ -288,6 +289,61 @@ def bilstm_limit(channels: int, units: int) -> str | None:
     return None
 
 
+@dataclass
+class MultiScaleConv:
+    """One MultiScaleConv1D (layers.py:1433-1595): ``len(branches)`` MaskedConv1Ds over the same rows of the (frames, length,
+    channels) tensor, every one with padding "same" and strides 1 (:1504-1505, :1517-1526) and its own kernel_size,
+    dilation_rate, activation, use_bias and mask_mode; their outputs concatenated along the channels (``merge`` "concat") or
+    summed in branch order (``merge`` "add", tf.add_n; :1539-1542).  The mask behind the layer is the AND of the branches'
+    output masks (:1544-1548), none where the branches do not mask or no mask arrives."""
+    name: str
+    cin: int
+    merge: str                     # "concat" | "add" (:1448)
+    branches: list                 # list[Conv], named <name>/branch<b>
+
+    @property
+    def channels(self) -> int:
+        """What the layer leaves: the branches side by side, or their common width."""
+        return sum(b.filters for b in self.branches) if self.merge == "concat" else self.branches[0].filters
+
+    @property
+    def use_masking(self) -> bool:
+        return self.branches[0].use_masking
+
+
+#: what the kernel (csrc/jg_msconv.hip) covers
+MSCONV_MAX_BRANCHES = 4
+MSCONV_MAX_CHANNELS = 128
+MSCONV_MAX_KERNEL = 15
+MSCONV_MAX_SPAN = 64
+# the constructor's own arguments (:1445-1453); the last three matter in training only
+_MSCONV_KEYS = {"branches", "merge", "use_bias", "kernel_initializer", "kernel_regularizer", "kernel_regularizer_w"}
+# MaskedConv1D's arguments (:1150-1168) a branch entry may carry
+_MSCONV_BRANCH_KEYS = {"filters", "kernel_size", "strides", "padding", "dilation_rate", "activation", "use_bias",
+                       "kernel_initializer", "bias_initializer", "kernel_regularizer", "axis",
+                       "use_masking", "mask_mode", "name", "dtype", "trainable"}
+
+
+def msconv_limit(cin: int, merge: str, branches: list) -> str | None:
+    """Why the multi-scale conv kernel cannot run this layer, or None."""
+    if cin % 16 or not 16 <= cin <= MSCONV_MAX_CHANNELS:
+        return f"{cin} incoming channels (a multiple of 16 up to {MSCONV_MAX_CHANNELS})"
+    if not 1 <= len(branches) <= MSCONV_MAX_BRANCHES:
+        return f"{len(branches)} branches (the kernel covers 1 to {MSCONV_MAX_BRANCHES})"
+    for b, c in enumerate(branches):
+        if c.filters % 8 or not 8 <= c.filters <= MSCONV_MAX_CHANNELS:
+            return f"branch {b}: filters {c.filters} (a multiple of 8 up to {MSCONV_MAX_CHANNELS})"
+        if not 1 <= c.kernel_size <= MSCONV_MAX_KERNEL:
+            return f"branch {b}: kernel_size {c.kernel_size} (the kernel covers 1 to {MSCONV_MAX_KERNEL})"
+        if c.dilation_rate < 1 or (c.kernel_size - 1) * c.dilation_rate > MSCONV_MAX_SPAN:
+            return (f"branch {b}: (kernel_size - 1) x dilation_rate = {(c.kernel_size - 1) * c.dilation_rate} "
+                    f"(dilation_rate at least 1, the product up to {MSCONV_MAX_SPAN})")
+    cout = sum(c.filters for c in branches) if merge == "concat" else branches[0].filters
+    if cout % 16 or not 16 <= cout <= MSCONV_MAX_CHANNELS:
+        return f"{cout} output channels (a multiple of 16 up to {MSCONV_MAX_CHANNELS})"
+    return None
+
+
 def _constructor_accepts(cfg: dict, keys: set) -> bool:
     """Whether the reference's constructor would take this config: the three required arguments are there and no key is
     an unknown keyword (keras.layers.Layer.__init__ raises on one)."""
@@ -556,6 +612,59 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
                                        "(the op's store carries no partial sums)")
             out.append(BiLstm(p, cin, units, bool(cfg.get("ignore_mask", False))))
             cin = 2 * units
+        elif name == "multi_scale_conv" and "branches" in cfg and not set(cfg) - _MSCONV_KEYS:
+            # builder.py:277-304, :1155: MultiScaleConv1D(**config); an entry without `branches` or with a key that is none of
+            # the constructor's arguments raises there and falls through to the generic refusal below.  The initialiser and
+            # the regulariser matter in training only
+            branches, merge = cfg["branches"], cfg.get("merge", "concat")
+            if not isinstance(branches, list) or len(branches) == 0 or not all(isinstance(b, dict) for b in branches):
+                raise ValueError(f"{p}: branches must be a non-empty list of dicts")                      # :1456-1459
+            if merge not in ("concat", "add"):
+                raise ValueError(f"{p}: merge must be 'concat' or 'add', got {merge!r}")                 # :1460-1461
+            if merge == "add" and len({b.get("filters") for b in branches}) != 1:
+                raise ValueError(f"{p}: All branches must have the same filters when merge='add'")        # :1495-1500
+            convs = []
+            for b, bcfg in enumerate(branches):
+                pad, strides = bcfg.get("padding", "same"), bcfg.get("strides", 1)                       # :1504-1505
+                if str(pad).lower() != "same":
+                    raise ValueError(f"{p}: Branch {b}: padding must be 'same' to keep sequence length aligned across "
+                                     f"branches, got {pad!r}")                                            # :1517-1521
+                if strides != 1:
+                    raise ValueError(f"{p}: Branch {b}: strides must be 1 to keep sequence length aligned across "
+                                     f"branches, got {strides!r}")                                        # :1522-1526
+                mode = bcfg.get("mask_mode", "any")
+                if mode not in ("any", "majority", "strict"):
+                    raise ValueError(f"{p}: Branch {b}: Invalid mask_mode: {mode!r} (use 'any', 'majority' or 'strict')")   # :1170-1173
+                if set(bcfg) - _MSCONV_BRANCH_KEYS:
+                    raise UnsupportedLayer(f"{p}: branch {b}: {sorted(set(bcfg) - _MSCONV_BRANCH_KEYS)} are no arguments of "
+                                           "MaskedConv1D (layers.py:1148-1165)")
+                if bcfg.get("axis", -1) != -1:
+                    raise UnsupportedLayer(f"{p}: branch {b}: axis {bcfg['axis']!r} (the kernel convolves along the length axis "
+                                           "with the channels last, axis = -1)")
+                # use_bias defaults to the layer's (:1515); use_masking to MaskedConv1D's own True (:1161): builder.py:1019-1020
+                # injects the model-level use_masking for masked_conv1d / masked_batchnorm / residual_block entries only
+                convs.append(Conv(f"{p}/branch{b}", int(bcfg["kernel_size"]), cin, int(bcfg["filters"]), 1, "same",
+                                  int(bcfg.get("dilation_rate", 1)), bool(bcfg.get("use_bias", cfg.get("use_bias", True))),
+                                  bcfg.get("activation"), bool(bcfg.get("use_masking", True)), mode))
+            if frames is None:
+                raise UnsupportedLayer(f"{p}: multi_scale_conv needs the (frames, length, channels) tensor of the "
+                                       "representation learner: not supported in a head or on a strand branch")
+            if len({c.use_masking for c in convs}) != 1:
+                raise UnsupportedLayer(f"{p}: multi_scale_conv whose branches disagree on use_masking (the reference ANDs a "
+                                       "branch's mask with None there, layers.py:1544-1548)")
+            why = msconv_limit(cin, merge, convs)
+            if why is not None:
+                raise UnsupportedLayer(f"{p}: multi_scale_conv with {why}")
+            nxt = layers[i + 1] if i + 1 < len(layers) else {}
+            if str(nxt.get("name", "")).lower() == "nmd" or (nxt.get("config") or {}).get("return_nmd"):
+                raise UnsupportedLayer(f"{p}: an nmd tap directly behind multi_scale_conv is not supported "
+                                       "(the op's store carries no partial sums)")
+            # builder.py:1161-1166 does not update previous_channels behind this layer (the entry has no top-level `filters`),
+            # so a residual_block that follows is constructed with a stale `shape` (:1075-1087).  That argument reaches
+            # ResidualBlockStack.__init__ as `in_shape` and is never read (layers.py:2658-2692, :2716-2721): the blocks build
+            # from the tensor they are called on.  The graph is the same, so such a block is accepted
+            out.append(MultiScaleConv(p, cin, merge, convs))
+            cin = out[-1].channels
         else:
             raise UnsupportedLayer(
                 f"{p}: layer {name!r} is outside the Conv1D -> norm -> pool -> dense family "
@@ -801,6 +910,8 @@ def weight_shapes(plan: ModelPlan) -> dict[str, tuple]:
                 out.update(hyena_weight_shapes(layer))
             elif isinstance(layer, BiLstm):
                 out.update(bilstm_weight_shapes(layer))
+            elif isinstance(layer, MultiScaleConv):
+                out.update(msconv_weight_shapes(layer))
             elif isinstance(layer, AxialAttn):
                 for j in range(layer.blocks):
                     out.update(length_attn_weight_shapes(layer.length(j)))
@@ -891,6 +1002,17 @@ def bilstm_weight_shapes(a: BiLstm) -> dict[str, tuple]:
         out[f"{a.name}/{d}/kernel"] = (a.cin, 4 * a.units)
         out[f"{a.name}/{d}/recurrent_kernel"] = (a.units, 4 * a.units)
         out[f"{a.name}/{d}/bias"] = (4 * a.units,)
+    return out
+
+
+def msconv_weight_shapes(a: MultiScaleConv) -> dict[str, tuple]:
+    """Keras variable shapes of one MultiScaleConv1D: per branch (``layer._convs[b]``, a MaskedConv1D) the kernel
+    (kernel_size, cin, filters) and, with use_bias, the bias (filters)."""
+    out: dict[str, tuple] = {}
+    for c in a.branches:
+        out[f"{c.name}/kernel"] = (c.kernel_size, c.cin, c.filters)
+        if c.use_bias:
+            out[f"{c.name}/bias"] = (c.filters,)
     return out
 
 

@@ -22,6 +22,8 @@ conv launches with epilogue stages:
   kept; its implicit filters are tabled here once (:func:`hyena_filter_tables`) and travel in the weight blob
 * ``masked_bilstm -> norm -> activation``                     one bilstm op (``layers.py:1335-1430``), out of place, rows of
   ``2 * units`` channels; the mask kept, or dropped with ``ignore_mask``
+* ``multi_scale_conv -> norm -> activation``                  one mask op (the AND of the branches' output masks) and one
+  multi-scale conv op (``layers.py:1433-1595``), out of place: every branch's conv, bias and activation and the concat / add
 
 Pure host logic (numpy + ctypes structs): unit-tested on CPU.
 """
@@ -33,7 +35,7 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 from . import _lib as L
-from .plan import HYENA_PE_DIM, Act, AxialAttn, BiLstm, Conv, Dense, FrameAttn, Hyena, LengthAttn, LocalAttn, ModelPlan, Nmd, Norm, ResBlock, UnsupportedLayer, weight_shapes
+from .plan import HYENA_PE_DIM, Act, AxialAttn, BiLstm, Conv, Dense, FrameAttn, Hyena, LengthAttn, LocalAttn, ModelPlan, MultiScaleConv, Nmd, Norm, ResBlock, UnsupportedLayer, weight_shapes
 
 _ACT_CODE = {None: L.ACT_NONE, "linear": L.ACT_NONE, "gelu": L.ACT_GELU_TANH, "gelu_erf": L.ACT_GELU_ERF,
              "relu": L.ACT_RELU, "tanh": L.ACT_TANH, "sigmoid": L.ACT_SIGMOID}
@@ -254,6 +256,38 @@ def pack_bilstm(a: BiLstm, w: dict[str, np.ndarray]) -> np.ndarray:
     return np.concatenate([x.ravel() for x in out]).astype(np.float32)
 
 
+def pack_msconv(a: MultiScaleConv, w: dict[str, np.ndarray]) -> np.ndarray:
+    """The blob of one MultiScaleConv1D as the two ops read it (csrc/jg_msconv.h): a descriptor of ``MSCONV_MAX_BRANCHES`` x
+    ``MSCONV_DESC_FIELDS`` int32 values stored as float32 BIT PATTERNS - per branch filters, taps, dilation, activation code,
+    mask mode, has-bias, channel offset in the output (0 for every branch under "add"), weight offset in floats from the
+    blob's start; unused branches zeros - then per branch the kernel ``[taps][cin][fpad]`` and the bias ``[fpad]``, fpad =
+    filters rounded up to 16, the padding columns and an absent bias zeros.  Nothing is folded."""
+    n = L.MSCONV_MAX_BRANCHES * L.MSCONV_DESC_FIELDS
+    desc = np.zeros((L.MSCONV_MAX_BRANCHES, L.MSCONV_DESC_FIELDS), np.int32)
+    parts, at, ch = [], n, 0
+    for b, c in enumerate(a.branches):
+        fpad = (c.filters + 15) // 16 * 16
+        kern = np.zeros((c.kernel_size, c.cin, fpad), np.float32)
+        kern[:, :, :c.filters] = np.asarray(w[f"{c.name}/kernel"], np.float32)
+        bias = np.zeros(fpad, np.float32)
+        if c.use_bias:
+            bias[:c.filters] = np.asarray(w[f"{c.name}/bias"], np.float32)
+        desc[b] = (c.filters, c.kernel_size, c.dilation_rate, act_code(c.activation), _MASK_MODE[c.mask_mode], int(c.use_bias),
+                   ch if a.merge == "concat" else 0, at)
+        parts += [kern.ravel(), bias]
+        at += kern.size + fpad
+        ch += c.filters
+    return np.concatenate([desc.ravel().view(np.float32)] + parts)
+
+
+def unpack_msconv_descriptor(blob: np.ndarray, n_branches: int) -> list[dict]:
+    """The descriptor at the head of a :func:`pack_msconv` blob, back as one dict per branch."""
+    fields = ("filters", "taps", "dilation", "activation", "mask_mode", "has_bias", "channel_offset", "weight_offset")
+    n = L.MSCONV_MAX_BRANCHES * L.MSCONV_DESC_FIELDS
+    desc = np.ascontiguousarray(blob[:n], np.float32).view(np.int32).reshape(L.MSCONV_MAX_BRANCHES, L.MSCONV_DESC_FIELDS)
+    return [dict(zip(fields, map(int, desc[b]))) for b in range(n_branches)]
+
+
 @dataclass
 class Program:
     ops: list            # list[L.JgOp]
@@ -283,7 +317,8 @@ class Program:
                         + (f" heads={op.k} ff={op.arg} half_window={op.stride}" if op.kind == L.OP_LOCALATTN else "")
                         + (f" heads={op.k} ff={op.arg}" if op.kind == L.OP_LENGTHATTN else "")
                         + (f" order={op.k} flags={op.arg} table_rows={op.stride}" if op.kind == L.OP_HYENA else "")
-                        + (f" units={op.k} ignore_mask={op.arg & L.BILSTM_IGNORE_MASK}" if op.kind == L.OP_BILSTM else ""))
+                        + (f" units={op.k} ignore_mask={op.arg & L.BILSTM_IGNORE_MASK}" if op.kind == L.OP_BILSTM else "")
+                        + (f" branches={op.k} merge={'add' if op.arg == L.MSCONV_ADD else 'concat'}" if op.kind in (L.OP_MSCONV, L.OP_MSMASK) else ""))
         return rows
 
 
@@ -448,7 +483,7 @@ class _Compiler:
                         w_off=self.blob.add(pack_length_attn(a, self.w)))
 
     def _emit_mixer(self, layers: list, i: int, what: str, buf: int, mask: int, out_mask: int, build_ops: list):
-        """A row-mixer layer (frame / local / length attention, hyena, bilstm) at ``layers[i]``: its ops - ``build_ops``, one
+        """A row-mixer layer (frame / local / length attention, hyena, bilstm, multi-scale conv) at ``layers[i]``: its ops - ``build_ops``, one
         ``(in_buf, out_buf) -> op`` per op, each into a fresh slot, never in place - with the bias / batch norm / unmasked
         DyT / activation layers that follow fused into the LAST op's store; a LayerNorm or a masked DyT is cut off into an
         element-wise op behind it.  ``out_mask``: the mask the layers behind see (the incoming one, or none where the layer
@@ -670,6 +705,25 @@ class _Compiler:
                     lambda src, dst: self._op(L.OP_BILSTM, in_buf=src, out_buf=dst, in_mask=mask, out_mask=out_mask, k=layer.units,
                                               cin=layer.cin, cout=layer.channels, arg=L.BILSTM_IGNORE_MASK if layer.ignore_mask else 0,
                                               w_off=self.blob.add(pack_bilstm(layer, self.w)))])
+            elif isinstance(layer, MultiScaleConv):
+                # Every branch is a MaskedConv1D (layers.py:1217-1280): it multiplies its input by the mask and convolves, so
+                # the layer reads valid positions only and writes defined values everywhere - it may stand behind a
+                # local_attention with live dead positions, and its output holds none (as behind a masked conv).  With
+                # use_masking false in all branches (or no mask) it reads every position, and no mask leaves it
+                masked = layer.use_masking and mask != L.JG_BUF_NONE
+                if masked:
+                    self.dead_margin = None
+                else:
+                    self._refuse_unmasked_reader(f"{layer.name}: multi_scale_conv whose branches do not mask" if mask != L.JG_BUF_NONE
+                                                 else f"{layer.name}: multi_scale_conv without a mask")
+                fields = dict(k=len(layer.branches), cin=layer.cin, cout=layer.channels,
+                              arg=L.MSCONV_ADD if layer.merge == "add" else L.MSCONV_CONCAT,
+                              w_off=self.blob.add(pack_msconv(layer, self.w)))
+                in_mask, out_mask = (mask, self.masks.take()) if masked else (L.JG_BUF_NONE, L.JG_BUF_NONE)
+                if masked:      # the layer's output-mask rule, in front of the op whose output it describes
+                    self.ops.append(self._op(L.OP_MSMASK, in_mask=in_mask, out_mask=out_mask, **fields))
+                i, buf, mask = self._emit_mixer(layers, i, "multi_scale_conv", buf, mask, out_mask, [
+                    lambda src, dst: self._op(L.OP_MSCONV, in_buf=src, out_buf=dst, in_mask=in_mask, out_mask=out_mask, **fields)])
             elif isinstance(layer, LengthAttn):
                 if buf == L.JG_BUF_IDS:
                     raise UnsupportedLayer(f"{layer.name}: transformer_encoder directly on the embedding is not supported")
@@ -731,7 +785,7 @@ class _Compiler:
                 c = layer.filters
             elif isinstance(layer, ResBlock):
                 c = layer.conv2.filters
-            elif isinstance(layer, BiLstm):
+            elif isinstance(layer, (BiLstm, MultiScaleConv)):
                 c = layer.channels
         return c
 
