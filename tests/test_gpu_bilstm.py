@@ -25,6 +25,7 @@ import pytest
 import attention_reference as ar
 import bilstm_reference as br
 from conftest import GOLDEN, load_model_cfg, make_model_dir
+from mixer_reference import producer
 from test_gpu_hyena import check_vectors, mask_writer
 
 pytestmark = pytest.mark.gpu
@@ -50,16 +51,6 @@ def _report():
 def bilstm_ops(prog):
     from jaeger_amd import _lib as L
     return [i for i, op in enumerate(prog.ops) if op.kind == L.OP_BILSTM]
-
-
-def producer(prog, i):
-    from jaeger_amd import _lib as L
-    slot = prog.ops[i].in_buf
-    for j in range(i - 1, -1, -1):
-        o = prog.ops[j]
-        if o.kind in (L.OP_CONV, L.OP_ELTWISE, L.OP_FRAMEATTN, L.OP_BILSTM, L.OP_EMBED) and o.out_buf == slot:
-            return j
-    raise AssertionError(f"op {i}: no producer of slot {slot}")
 
 
 def layers_of(cfg, prog):

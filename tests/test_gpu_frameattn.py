@@ -23,6 +23,7 @@ import pytest
 
 import attention_reference as ar
 from conftest import GOLDEN, load_model_cfg, make_model_dir
+from mixer_reference import producer
 
 pytestmark = pytest.mark.gpu
 
@@ -129,16 +130,6 @@ def check_vectors(what, got, ref):
 def attention_ops(prog):
     from jaeger_amd import _lib as L
     return [i for i, op in enumerate(prog.ops) if op.kind == L.OP_FRAMEATTN]
-
-
-def producer(prog, i):
-    from jaeger_amd import _lib as L
-    slot = prog.ops[i].in_buf
-    for j in range(i - 1, -1, -1):
-        o = prog.ops[j]
-        if o.kind in (L.OP_CONV, L.OP_ELTWISE, L.OP_FRAMEATTN, L.OP_EMBED) and o.out_buf == slot:
-            return j
-    raise AssertionError(f"op {i}: no producer of slot {slot}")
 
 
 @pytest.mark.parametrize("precision", ["f16x3", "f32"])

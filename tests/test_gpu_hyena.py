@@ -24,6 +24,7 @@ import pytest
 import attention_reference as ar
 import hyena_reference as hr
 from conftest import GOLDEN, load_model_cfg, make_model_dir
+from mixer_reference import mask_writer, producer
 
 pytestmark = pytest.mark.gpu
 
@@ -131,29 +132,6 @@ def check_vectors(what, got, ref):
 def hyena_ops(prog):
     from jaeger_amd import _lib as L
     return [i for i, op in enumerate(prog.ops) if op.kind == L.OP_HYENA]
-
-
-def producer(prog, i):
-    from jaeger_amd import _lib as L
-    slot = prog.ops[i].in_buf
-    for j in range(i - 1, -1, -1):
-        o = prog.ops[j]
-        if o.kind in (L.OP_CONV, L.OP_ELTWISE, L.OP_FRAMEATTN, L.OP_HYENA, L.OP_EMBED) and o.out_buf == slot:
-            return j
-    raise AssertionError(f"op {i}: no producer of slot {slot}")
-
-
-def mask_writer(prog, i):
-    from jaeger_amd import _lib as L
-    slot = prog.ops[i].in_mask
-    if slot == L.JG_BUF_NONE:
-        return None
-    for j in range(i - 1, -1, -1):
-        o = prog.ops[j]
-        if o.kind in (L.OP_MASK, L.OP_EMBED) and o.out_mask == slot:
-            assert o.kind == L.OP_MASK
-            return j
-    raise AssertionError(f"op {i}: no writer of mask slot {slot}")
 
 
 def layers_of(cfg, prog):

@@ -24,6 +24,7 @@ import pytest
 import attention_reference as ar
 import multiscale_reference as mr
 from conftest import GOLDEN, load_model_cfg, make_model_dir
+from mixer_reference import mask_writer, producer
 from test_gpu_hyena import check_vectors
 
 pytestmark = pytest.mark.gpu
@@ -48,30 +49,6 @@ def _report():
 
 def ops_of_kind(prog, kind):
     return [i for i, op in enumerate(prog.ops) if op.kind == kind]
-
-
-def producer(prog, i):
-    from jaeger_amd import _lib as L
-    slot = prog.ops[i].in_buf
-    for j in range(i - 1, -1, -1):
-        o = prog.ops[j]
-        if o.kind in (L.OP_CONV, L.OP_ELTWISE, L.OP_FRAMEATTN, L.OP_LOCALATTN, L.OP_MSCONV, L.OP_EMBED) and o.out_buf == slot:
-            return j
-    raise AssertionError(f"op {i}: no producer of slot {slot}")
-
-
-def mask_writer(prog, i):
-    """The op that wrote the mask slot op i reads (None: it reads none)."""
-    from jaeger_amd import _lib as L
-    slot = prog.ops[i].in_mask
-    if slot == L.JG_BUF_NONE:
-        return None
-    for j in range(i - 1, -1, -1):
-        o = prog.ops[j]
-        if o.kind in (L.OP_MASK, L.OP_MSMASK, L.OP_EMBED) and o.out_mask == slot:
-            assert o.kind != L.OP_EMBED
-            return j
-    raise AssertionError(f"op {i}: no writer of mask slot {slot}")
 
 
 def layers_of(cfg, prog):
