@@ -139,6 +139,20 @@ typedef enum {
                           count c of set in_mask bytes among the positions t + j d - (taps - 1) d // 2 inside the row
                           (layers.py:1237-1254, :1544-1548).  cin, cout, k, arg and w_off as in the JG_OP_MSCONV it belongs
                           to (the same descriptor, validated the same way); no activation slot is read or written */
+  JG_OP_POOLVEC = 20,   /* pool-and-merge: one masked global pool of in_buf under in_mask over the (frames, L) rows of a window,
+                          merged into out_vec[vec_off .. vec_off + cout) - a pooled branch of parallel_branches
+                          (nnlib/builder.py:1109-1153) and MaskedLastPooling (nnlib/v2/layers.py:541-578).  arg = the pool
+                          (jg_pool_kind): JG_POOL_MAX and JG_POOL_AVG with JG_OP_POOL's formulas (the -1e9 sentinel, zeros for a
+                          window without a valid position; sum / max(count, 1e-7)); JG_POOL_LAST: per frame row idx = (number of
+                          set in_mask bytes) - 1 - the count, not the index of the last valid position, as the reference's code has
+                          it -, the row's value at max(idx, 0) whatever its mask byte, rows with idx < 0 add zeros, the sum over
+                          the frames divided by max(rows with idx >= 0, 1); without a mask the mean over the frames of position
+                          L - 1.  k = how the pooled vector r meets what the range holds (jg_poolvec_merge): v = r, old + r or
+                          max(old, r); the range then holds v * f0 (1 / n on the last branch of an average, 1 elsewhere).  The ops
+                          of a program run in order: the branch order fixes the float32 result.  cout = the channels of in_buf;
+                          cout and vec_off multiples of 4, vec_off + cout up to 1 024; add / max only into a range an earlier op
+                          of the program wrote: jg_model_create refuses anything else with the reason.  No activation slot or
+                          mask is written */
   JG_OP_STRANDS = 10  /* a branched (shared-weight) model over the k strands of a nucleotide input: every strand is a
                           program row of its own (ids (W, k, L), one frame per row); arg = how the strands' predictions
                           merge (jg_merge_kind); the embedding output is their average.  builder.py:1195-1266, :776-791 */
@@ -167,7 +181,8 @@ typedef enum {
 
 typedef enum { JG_MASK_ANY = 0, JG_MASK_MAJORITY = 1, JG_MASK_STRICT = 2 } jg_mask_mode;
 typedef enum { JG_PAD_VALID = 0, JG_PAD_SAME = 1 } jg_padding;
-typedef enum { JG_POOL_MAX = 0, JG_POOL_AVG = 1, JG_POOL_MAX_NOMASK = 2 } jg_pool_kind;
+typedef enum { JG_POOL_MAX = 0, JG_POOL_AVG = 1, JG_POOL_MAX_NOMASK = 2, JG_POOL_LAST = 3 /* JG_OP_POOLVEC only */ } jg_pool_kind;
+typedef enum { JG_POOLVEC_STORE = 0, JG_POOLVEC_ADD = 1, JG_POOLVEC_MAX = 2 } jg_poolvec_merge;   /* JG_OP_POOLVEC's k */
 typedef enum { JG_MERGE_AVERAGE = 0, JG_MERGE_SUM = 1, JG_MERGE_MAX = 2, JG_MERGE_CONCAT = 3 } jg_merge_kind;   /* CONCAT (round 6): builder.py:1262-1265 */
 
 /* buffer slot constants */

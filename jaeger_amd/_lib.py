@@ -40,7 +40,7 @@ JG_PROF_MFMA_F16X3, JG_PROF_MFMA_F32, JG_PROF_TABLE, JG_PROF_FUSED_SMALL, JG_PRO
 TAP_F16S, TAP_PHASE_SPLIT, TAP_WINDOW_PACKED, TAP_TABLE_LOOKUP, TAP_NARROW, TAP_EXACT_F32, TAP_FUSED_RESBLOCK = 1, 2, 4, 8, 16, 32, 64
 
 # jg_op_kind
-OP_CONV, OP_MASK, OP_POOL, OP_DENSE, OP_ELTWISE, OP_NMD_FINAL, OP_OODSIG, OP_MAXPOOL1D, OP_FRAMESUM, OP_STRANDS, OP_EMBED, OP_VECMAX, OP_FRAMEATTN, OP_LOCALATTN, OP_LENGTHATTN, OP_HYENA, OP_BILSTM, OP_MSCONV, OP_MSMASK = range(1, 20)
+OP_CONV, OP_MASK, OP_POOL, OP_DENSE, OP_ELTWISE, OP_NMD_FINAL, OP_OODSIG, OP_MAXPOOL1D, OP_FRAMESUM, OP_STRANDS, OP_EMBED, OP_VECMAX, OP_FRAMEATTN, OP_LOCALATTN, OP_LENGTHATTN, OP_HYENA, OP_BILSTM, OP_MSCONV, OP_MSMASK, OP_POOLVEC = range(1, 21)
 LOCALATTN_TILE = 80          # jg_localattn_tile(): query positions of one work item of the local-attention kernel
 LOCALATTN_MAX_HALF = 32
 LENGTHATTN_TILE, LENGTHATTN_CHUNK = 128, 64      # jg_lengthattn_tile(), jg_lengthattn_chunk()
@@ -58,7 +58,9 @@ ST_NONE, ST_BIAS, ST_BN, ST_DYT, ST_ADD, ST_ACT, ST_NMD, ST_MASKMUL, ST_LN = ran
 ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF, ACT_RELU, ACT_TANH, ACT_SIGMOID = range(6)
 MASK_ANY, MASK_MAJORITY, MASK_STRICT = range(3)
 PAD_VALID, PAD_SAME = 0, 1
-POOL_MAX, POOL_AVG, POOL_MAX_NOMASK = 0, 1, 2
+POOL_MAX, POOL_AVG, POOL_MAX_NOMASK, POOL_LAST = 0, 1, 2, 3      # POOL_LAST: JG_OP_POOLVEC only
+POOLVEC_STORE, POOLVEC_ADD, POOLVEC_MAX = 0, 1, 2                  # JG_OP_POOLVEC's k: the merge code
+POOLVEC_MAX_WIDTH = 1024                                         # floats of a vector slot a pool-and-merge op may fill
 MERGE_AVERAGE, MERGE_SUM, MERGE_MAX, MERGE_CONCAT = 0, 1, 2, 3            # jg_merge_kind (OP_STRANDS)
 JG_ENC_PRECASED, JG_ENC_CASE_SENSITIVE, JG_ENC_NUCLEOTIDE, JG_ENC_DICODON = 1, 2, 4, 8   # jg_encode / jg_predict_windows soft_mask bits
 # vector slot convention (jg_model.hip: jg_model_vec_width)

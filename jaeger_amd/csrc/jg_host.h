@@ -16,6 +16,7 @@
 #include "jg_hyena.h"
 #include "jg_bilstm.h"
 #include "jg_msconv.h"
+#include "jg_poolvec.h"
 
 #pragma GCC visibility push(hidden)
 // ---- shapes: jg_shape_walk (jg_model.hip) is the only place that computes them -------------------------------------

@@ -175,6 +175,41 @@ static int validate_mixer(const jg_model *m, size_t i, const float *weights) {
   return JG_OK;
 }
 
+// a pool-and-merge op: arg = the pool, k = the merge, f0 = the scale, cout channels of in_buf into out_vec at vec_off
+static int validate_poolvec(const jg_model *m, size_t i) {
+  const jg_op &op = m->ops[i];
+  JG_REQUIRE(op.in_buf >= 0 && op.out_vec >= 0 && (op.in_mask >= 0 || op.in_mask == JG_BUF_NONE), JG_ERR_INVALID,
+             "op %zu: a pool-and-merge op reads an activation slot under a mask slot or none and writes a vector slot", i);
+  char why[200];
+  JG_REQUIRE(jg_poolvec_supports(op.arg, op.k, op.cout, op.vec_off, why, sizeof(why)), JG_ERR_UNSUPPORTED,
+             "op %zu: pool-and-merge with %s", i, why);
+  JG_REQUIRE(m->ops.back().kind != JG_OP_STRANDS, JG_ERR_UNSUPPORTED,
+             "op %zu: pool-and-merge needs the frame rows of a translated window (not a strand program)", i);
+  // the channels of the tensor it pools: what the last writer of the slot leaves (the two ops that keep the width: their input's)
+  int buf = op.in_buf, channels = -1;
+  for (size_t j = i; j-- > 0 && channels < 0;) {
+    const jg_op &o = m->ops[j];
+    if (!jg_op_writes(o, buf)) continue;
+    if (o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM) buf = o.in_buf;
+    else channels = o.cout;
+  }
+  JG_REQUIRE(channels == op.cout, JG_ERR_INVALID, "op %zu: pool-and-merge of %d channels, activation slot %d holds %d", i, op.cout,
+             op.in_buf, channels);
+  if (op.k != JG_POOLVEC_STORE) {
+    bool written = false;
+    for (size_t j = 0; j < i && !written; ++j) {
+      const jg_op &o = m->ops[j];
+      written = o.out_vec == op.out_vec && o.vec_off <= op.vec_off && o.vec_off + o.cout >= op.vec_off + op.cout &&
+                (o.kind == JG_OP_POOLVEC || o.kind == JG_OP_POOL || o.kind == JG_OP_DENSE || o.kind == JG_OP_NMD_FINAL ||
+                 o.kind == JG_OP_VECMAX || o.kind == JG_OP_OODSIG);
+    }
+    JG_REQUIRE(written, JG_ERR_INVALID, "op %zu: pool-and-merge %s into floats %d .. %d of vector slot %d, which no earlier op of the program wrote",
+               i, op.k == JG_POOLVEC_ADD ? "adds" : "maximises", op.vec_off, op.vec_off + op.cout, op.out_vec);
+  }
+  JG_REQUIRE(op.n_stages == 0, JG_ERR_UNSUPPORTED, "op %zu: a pool-and-merge op carries no stages", i);
+  return JG_OK;
+}
+
 static int validate_program(const jg_model *m, const float *weights) {
   int rc;
   for (size_t i = 0; i < m->ops.size(); ++i) {
@@ -182,7 +217,7 @@ static int validate_program(const jg_model *m, const float *weights) {
     auto slot_ok = [](int s, bool allow_ids) {
       return (s >= 0 && s < JG_MAX_BUFS) || s == JG_BUF_NONE || (allow_ids && s == JG_BUF_IDS);
     };
-    JG_REQUIRE(op.kind >= JG_OP_CONV && op.kind <= JG_OP_MSMASK, JG_ERR_INVALID,
+    JG_REQUIRE(op.kind >= JG_OP_CONV && op.kind <= JG_OP_POOLVEC, JG_ERR_INVALID,
                "op %zu: unknown kind %d", i, op.kind);
     if (op.kind == JG_OP_VECMAX)
       JG_REQUIRE(op.in_vec >= 0 && op.out_vec >= 0 && op.in_vec != op.out_vec && op.k >= 1 && op.cout >= 1 && op.vec_off >= 0,
@@ -227,6 +262,7 @@ static int validate_program(const jg_model *m, const float *weights) {
       JgMsconvDesc d;
       if ((rc = msconv_desc(m, i, weights, &d)) != JG_OK) return rc;
     }
+    if (op.kind == JG_OP_POOLVEC && (rc = validate_poolvec(m, i)) != JG_OK) return rc;
     if (op.kind == JG_OP_DENSE) {
       JG_REQUIRE(off_ok(op.w_off, (int64_t)op.cin * op.cout), JG_ERR_INVALID,
                  "op %zu: dense kernel outside the weight blob", i);
@@ -330,6 +366,15 @@ int jg_shape_walk(const jg_model *m, int l, std::vector<OpShape> &shp) {
         JG_REQUIRE(op.out_vec >= 0, JG_ERR_INVALID, "op %zu: pool needs an output vector", i);
         r.vec_need = op.vec_off + r.in.C;
         break;
+      case JG_OP_POOLVEC:
+        JG_REQUIRE(r.in.C == op.cout && r.in.frames >= 1 && r.in.frames <= JG_POOLVEC_MAX_FRAMES, JG_ERR_INVALID,
+                   "op %zu: pool-and-merge of %d channels over (%d, L, %d) rows", i, op.cout, r.in.frames, r.in.C);
+        if (op.in_mask >= 0) {
+          r.m_in = mL[op.in_mask];
+          JG_REQUIRE(r.m_in == r.in.L, JG_ERR_INVALID, "op %zu: pool-and-merge over rows of %d positions with a mask of %d", i, r.in.L, r.m_in);
+        }
+        r.vec_need = op.vec_off + op.cout;
+        break;
       case JG_OP_DENSE:
         JG_REQUIRE(op.in_vec >= 0 && op.out_vec >= 0, JG_ERR_INVALID, "op %zu: dense vectors", i);
         JG_REQUIRE(vw[op.in_vec] >= op.cin, JG_ERR_INVALID, "op %zu: dense expects %d inputs, vector %d has %d", i, op.cin, op.in_vec, vw[op.in_vec]);
@@ -431,6 +476,14 @@ extern "C" int jg_model_describe(const jg_model *m, char *buf, int64_t cap) {
       mixer_describe(op, i, line, sizeof(line));
       out += line;
       out += (m->f16_eligible && m->hprep[i].n_cvt > 0) ? " (F16S -> f32 conversion in front)\n" : "\n";
+      continue;
+    }
+    if (op.kind == JG_OP_POOLVEC) {
+      static const char *const pool_name[] = {"max", "average", "?", "last"}, *const merge_name[] = {"store", "add", "max"};
+      snprintf(line, sizeof(line), "op %zu: pool-and-merge %s c=%d %s -> vector %d [%d, %d) %s x %g, one workgroup a window, f32 rows\n", i,
+               pool_name[op.arg & 3], op.cout, op.in_mask >= 0 ? "masked" : "no mask", op.out_vec, op.vec_off, op.vec_off + op.cout,
+               merge_name[op.k % 3], (double)op.f0);
+      out += line;
       continue;
     }
     if (op.kind != JG_OP_CONV) continue;
@@ -801,7 +854,7 @@ extern "C" int jg_model_vec_width(const jg_model *m, int which) {
   for (const jg_op &op : m->ops) {
     if (op.out_vec != slot) continue;
     int wd = 0;
-    if (op.kind == JG_OP_DENSE || op.kind == JG_OP_NMD_FINAL || op.kind == JG_OP_VECMAX || op.kind == JG_OP_POOL) wd = op.vec_off + op.cout;
+    if (op.kind == JG_OP_DENSE || op.kind == JG_OP_NMD_FINAL || op.kind == JG_OP_VECMAX || op.kind == JG_OP_POOL || op.kind == JG_OP_POOLVEC) wd = op.vec_off + op.cout;
     width = std::max(width, wd);
   }
   // a branched model whose classifier's merge layer is Concatenate (builder.py:1262-1265): the window's prediction is the

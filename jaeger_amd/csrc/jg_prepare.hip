@@ -333,7 +333,7 @@ int jg_prepare_f32(jg_model *m, const float *weights) {
 // all go by these two.
 bool jg_op_reads(const jg_op &o, int buf) {
   if ((o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE || o.kind == JG_OP_MAXPOOL1D || o.kind == JG_OP_FRAMESUM || o.kind == JG_OP_POOL ||
-       o.kind == JG_OP_NMD_FINAL || jg_op_is_mixer(o.kind)) && o.in_buf == buf)
+       o.kind == JG_OP_POOLVEC || o.kind == JG_OP_NMD_FINAL || jg_op_is_mixer(o.kind)) && o.in_buf == buf)
     return true;
   if (o.kind == JG_OP_CONV || o.kind == JG_OP_ELTWISE)
     for (int q = 0; q < o.n_stages; ++q)
@@ -694,6 +694,9 @@ int jg_prepare_f16(jg_model *m, const float *weights) {
         break;
       case JG_OP_POOL:
         if (m->pool_fused_by[i] < 0) need(i, op.in_buf, true);
+        break;
+      case JG_OP_POOLVEC:                               // f32 rows, never fused into its producer's epilogue
+        need(i, op.in_buf, true);
         break;
       default:
         if (!jg_op_is_mixer(op.kind)) break;            // f32 rows in and out: an F16S producer is converted in front of it

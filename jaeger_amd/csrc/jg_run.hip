@@ -571,6 +571,15 @@ static int launch_ordinary(jg_model *m, size_t i, const OpShape &r, const uint8_
     case JG_OP_POOL:
       return jg_launch_pool(m->act[op.in_buf], op.in_mask >= 0 ? m->msk[op.in_mask] : nullptr, nw, in.frames * in.L, in.C, op.arg,
                             out_vec + op.vec_off, out_ld, s);
+    case JG_OP_POOLVEC: {
+      JgPoolVecArgs a;
+      memset(&a, 0, sizeof(a));
+      a.x = m->act[op.in_buf]; a.mask = op.in_mask >= 0 ? m->msk[op.in_mask] : nullptr;
+      a.out = out_vec + op.vec_off; a.out_ld = out_ld;
+      a.n_win = nw; a.frames = in.frames; a.L = in.L; a.c = in.C;
+      a.kind = op.arg; a.merge = op.k; a.scale = op.f0;
+      return jg_launch_poolvec(a, s);
+    }
     case JG_OP_DENSE:
       return jg_launch_dense(m->vec[op.in_vec], m->vec_w[op.in_vec], m->d_w + op.w_off, op.b_off >= 0 ? m->d_w + op.b_off : nullptr,
                              nw, op.cin, op.cout, op.arg, out_vec + op.vec_off, out_ld, s);

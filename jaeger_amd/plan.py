@@ -6,8 +6,8 @@ in ``nnlib/builder.py`` (``build_fragment_classifier`` :442-838,
 :1697-1714).  This module resolves the same section into a flat, fully
 defaulted plan (every default below cites the constructor it comes from) that
 ``program.py`` compiles for the MI355X engine.  Layers outside the conv family
-(gated / last pooling, parallel branches ...) raise :class:`UnsupportedLayer`; the attention layers, ``hyena_block``,
-``masked_bilstm`` and ``multi_scale_conv`` are plan nodes of their own.
+(gated pooling ...) raise :class:`UnsupportedLayer`; the attention layers, ``hyena_block``, ``masked_bilstm``,
+``multi_scale_conv`` and ``parallel_branches`` are plan nodes of their own.
 
 Canonical weight names (shared with the loaders in ``weights.py``):
 ``embedding/embeddings``; ``rep/<i>/{kernel,bias,gamma,beta,moving_mean,
@@ -15,6 +15,8 @@ moving_variance,alpha}`` for the i-th ``hidden_layers`` entry;
 ``rep/<i>/block<j>/{conv1,conv2,conv3,bn1,bn2,bn3}/<var>`` inside a
 ``residual_block``; ``rep/<i>/{forward,backward}/{kernel,recurrent_kernel,bias}`` for a ``masked_bilstm``;
 ``rep/<i>/branch<b>/{kernel,bias}`` for the b-th branch of a ``multi_scale_conv``;
+``rep/<i>/branch<b>/<j>/...`` for the j-th ``hidden_layers`` entry of the b-th branch of a ``parallel_branches``, by the same
+rules as ``rep/<j>/...``;
 ``classifier/<i>/...`` and ``reliability/<i>/...`` for the heads.
 """
 
@@ -344,6 +346,50 @@ def msconv_limit(cin: int, merge: str, branches: list) -> str | None:
     return None
 
 
+@dataclass
+class Branch:
+    """One entry of ``parallel_branches.branches``: a block of its own on the layer's input (builder.py:1116-1122)."""
+    layers: list                   # the compiled ``hidden_layers``, named <name>/branch<b>/<j>
+    pooling: str                   # "max" | "average" | "last"
+    channels: int                  # what the branch's pooled vector holds
+
+
+@dataclass
+class ParallelBranches:
+    """One ``parallel_branches`` entry (builder.py:1109-1153): every branch a recursive ``_build_block`` on the same tensor
+    under the same mask, with ``nmd_merge=None`` and a tuple result cut to its first element - NMD taps inside a branch are
+    built and dropped -; the branch outputs merged in branch order: ``concat`` along the channels, ``sum`` (Add: a running
+    sum), ``average`` (Average: that sum divided by the number of branches), ``max`` (Maximum: a running maximum).  Here every
+    branch pools, so the layer leaves a (B, C) vector: it closes the representation learner, whose own pooling is null."""
+    name: str
+    merge: str                     # "concat" | "sum" | "average" | "max"
+    branches: list                 # list[Branch]
+
+    @property
+    def channels(self) -> int:
+        """The merged width: the branches side by side, or their common width."""
+        return sum(b.channels for b in self.branches) if self.merge == "concat" else self.branches[0].channels
+
+
+#: what the pool-and-merge op (csrc/jg_poolvec.hip) covers
+BRANCHES_MAX = 4
+BRANCHES_MAX_WIDTH = 1024          # floats of the merged vector: the pool kernels' limit, inside what the dense kernels read
+BRANCH_MERGES = ("concat", "sum", "average", "max")
+_POOLINGS = {"max": "max", "masked_max": "max", "average": "average", "masked_average": "average", "last": "last",
+             "masked_last": "last"}                                          # builder.py:1703-1712
+_BRANCHES_KEYS = {"merge", "branches"}                                       # what builder.py:1110-1111 reads
+_BRANCH_KEYS = {"hidden_layers", "pooling"}                                  # what _build_block reads (:1007, :1169)
+
+
+class _DropTaps:
+    """``_block``'s ``nmd_dims`` where the reference builds NMD taps and drops them (inside a ``parallel_branches`` branch,
+    and in front of one that closes the block: builder.py:1124-1125, :1169-1193): ``nmd`` layers vanish, ``return_nmd`` norms
+    and blocks compute what they compute without the side output."""
+
+
+DROP_TAPS = _DropTaps()
+
+
 def _constructor_accepts(cfg: dict, keys: set) -> bool:
     """Whether the reference's constructor would take this config: the three required arguments are there and no key is
     an unknown keyword (keras.layers.Layer.__init__ raises on one)."""
@@ -355,7 +401,7 @@ class ModelPlan:
     vocab: int
     embedding_dim: int
     rep: list[Any]
-    pooling: str                   # "max" | "average"
+    pooling: str | None            # "max" | "average" | "last"; None: the last rep layer is a parallel_branches of pooled branches
     rep_channels: int
     classifier: list[Any]
     n_classes: int
@@ -409,10 +455,14 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
     """builder.py:982-1158: walk one ``hidden_layers`` list.  ``frames``: the frame axis of the tensor the list runs on
     (the representation learner of a translated model), None where there is none (heads, strand branches)."""
     out: list[Any] = []
+    drop = nmd_dims is DROP_TAPS
     for i, layer in enumerate(layers):
         name = str(layer.get("name", "")).lower()
         cfg = dict(layer.get("config", {}) or {})
         p = f"{prefix}/{i}"
+        if out and isinstance(out[-1], ParallelBranches) and name != "dropout":
+            raise UnsupportedLayer(f"{p}: layer {name!r} behind a parallel_branches of pooled branches (the merged (B, C) vector "
+                                   "goes to the heads: only dropout may follow)")
         if name == "conv1d":
             # tf.keras.layers.Conv1D (builder.py:280): strides 1, padding "valid", dilation 1, bias, no activation, and no
             # mask handling of its own - an incoming Keras mask is dropped
@@ -435,7 +485,7 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
         elif name in _NORMS:
             um = bool(cfg.get("use_masking", use_masking_default)) if name == "masked_batchnorm" else True
             norm = _norm(p, name, cin, cfg, um)
-            if cfg.get("return_nmd"):
+            if cfg.get("return_nmd") and not drop:
                 # MaskedBatchNorm(return_nmd=True) also returns the masked per-example channel mean of its INPUT
                 # minus its own moving_mean (layers.py:943-954): an NMD tap in front of the norm that shares the
                 # norm's moving_mean and epsilon
@@ -445,6 +495,8 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
                 nmd_dims.append(cin)
             out.append(norm)
         elif name == "nmd":
+            if drop:
+                continue                                        # built on the side and dropped: the tensor passes unchanged
             if nmd_dims is None:
                 raise UnsupportedLayer(f"{p}: nmd layer outside the representation learner")
             out.append(Nmd(p, cin, float(cfg.get("epsilon", 1e-5))))
@@ -481,8 +533,9 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
                         raise ValueError(f"{p}: return_nmd=True is only supported with norm_type='masked_batchnorm'")
                     if nmd_dims is None:
                         raise UnsupportedLayer(f"{p}: return_nmd block outside the representation learner")
-                    blk.nmd = Nmd(f"{bp}/bn2", filters, blk.bn2.epsilon)
-                    nmd_dims.append(filters)
+                    if not drop:
+                        blk.nmd = Nmd(f"{bp}/bn2", filters, blk.bn2.epsilon)
+                        nmd_dims.append(filters)
                 out.append(blk)
                 cin = filters
         elif name == "dense":
@@ -585,7 +638,7 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
             if seq_len is not None and int(seq_len) < 1:
                 raise UnsupportedLayer(f"{p}: hyena_block seq_len {seq_len} (a positive number of positions, or none)")
             nxt = layers[i + 1] if i + 1 < len(layers) else {}
-            if str(nxt.get("name", "")).lower() == "nmd" or (nxt.get("config") or {}).get("return_nmd"):
+            if not drop and (str(nxt.get("name", "")).lower() == "nmd" or (nxt.get("config") or {}).get("return_nmd")):
                 raise UnsupportedLayer(f"{p}: an nmd tap directly behind hyena_block is not supported "
                                        "(the op's store carries no partial sums)")
             out.append(Hyena(p, c, order, int(cfg.get("filter_hidden", 32)), fl,
@@ -607,7 +660,7 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
             if why is not None:
                 raise UnsupportedLayer(f"{p}: masked_bilstm with {why}")
             nxt = layers[i + 1] if i + 1 < len(layers) else {}
-            if str(nxt.get("name", "")).lower() == "nmd" or (nxt.get("config") or {}).get("return_nmd"):
+            if not drop and (str(nxt.get("name", "")).lower() == "nmd" or (nxt.get("config") or {}).get("return_nmd")):
                 raise UnsupportedLayer(f"{p}: an nmd tap directly behind masked_bilstm is not supported "
                                        "(the op's store carries no partial sums)")
             out.append(BiLstm(p, cin, units, bool(cfg.get("ignore_mask", False))))
@@ -656,7 +709,7 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
             if why is not None:
                 raise UnsupportedLayer(f"{p}: multi_scale_conv with {why}")
             nxt = layers[i + 1] if i + 1 < len(layers) else {}
-            if str(nxt.get("name", "")).lower() == "nmd" or (nxt.get("config") or {}).get("return_nmd"):
+            if not drop and (str(nxt.get("name", "")).lower() == "nmd" or (nxt.get("config") or {}).get("return_nmd")):
                 raise UnsupportedLayer(f"{p}: an nmd tap directly behind multi_scale_conv is not supported "
                                        "(the op's store carries no partial sums)")
             # builder.py:1161-1166 does not update previous_channels behind this layer (the entry has no top-level `filters`),
@@ -665,11 +718,69 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
             # from the tensor they are called on.  The graph is the same, so such a block is accepted
             out.append(MultiScaleConv(p, cin, merge, convs))
             cin = out[-1].channels
+        elif name == "parallel_branches":
+            out.append(_parallel_branches(p, cfg, cin, use_masking_default, nmd_dims, frames))
+            cin = out[-1].channels
         else:
             raise UnsupportedLayer(
                 f"{p}: layer {name!r} is outside the Conv1D -> norm -> pool -> dense family "
                 "the MI355X engine implements")
     return out, cin
+
+
+def _parallel_branches(p: str, cfg: dict, cin: int, use_masking_default: bool, nmd_dims, frames: int | None) -> ParallelBranches:
+    """builder.py:1109-1153.  The reference's two ValueErrors keep their wording; what Keras' merge layers refuse is a
+    ValueError too; what this engine does not run is an UnsupportedLayer with the reason."""
+    merge = str(cfg.get("merge", "concat")).lower()
+    branch_cfgs = cfg.get("branches", [])
+    if not branch_cfgs:
+        raise ValueError("parallel_branches requires at least one branch")                               # :1112-1113
+    if merge not in BRANCH_MERGES:
+        raise ValueError(f"Unknown parallel_branches merge method: {merge}")                             # :1143-1145
+    if nmd_dims is None or frames is None:
+        raise UnsupportedLayer(f"{p}: parallel_branches needs the (frames, length, channels) tensor of the representation "
+                               "learner: not supported in a head or on a strand branch")
+    if set(cfg) - _BRANCHES_KEYS:
+        raise UnsupportedLayer(f"{p}: parallel_branches keys {sorted(set(cfg) - _BRANCHES_KEYS)} (the builder reads "
+                               f"{' / '.join(sorted(_BRANCHES_KEYS))})")
+    if not isinstance(branch_cfgs, list) or not all(isinstance(b, dict) for b in branch_cfgs):
+        raise UnsupportedLayer(f"{p}: parallel_branches branches must be a list of blocks (hidden_layers, pooling)")
+    if len(branch_cfgs) > BRANCHES_MAX:
+        raise UnsupportedLayer(f"{p}: parallel_branches with {len(branch_cfgs)} branches (up to {BRANCHES_MAX})")
+    pooled = [b.get("pooling") is not None for b in branch_cfgs]
+    if any(pooled) and not all(pooled):
+        raise UnsupportedLayer(f"{p}: parallel_branches that mixes pooled and unpooled branches (a (B, C) vector cannot be "
+                               "merged with a (B, frames, L, C) tensor)")
+    branches = []
+    for b, bcfg in enumerate(branch_cfgs):
+        bp = f"{p}/branch{b}"
+        if set(bcfg) - _BRANCH_KEYS:
+            raise UnsupportedLayer(f"{bp}: branch keys {sorted(set(bcfg) - _BRANCH_KEYS)} (a branch is a block of "
+                                   f"{' / '.join(sorted(_BRANCH_KEYS))})")
+        if bcfg.get("pooling") is None:
+            raise UnsupportedLayer(f"{bp}: a branch without pooling is not supported (the mask of the merged tensor is decided "
+                                   "by Keras' merge layers, whose rule could not be pinned here)")
+        raw = str(bcfg["pooling"]).lower()
+        if "gated" in raw:
+            raise UnsupportedLayer(f"{bp}: pooling {raw!r} in a branch is not supported (its gate output has no place in a merge)")
+        if raw not in _POOLINGS:
+            raise UnsupportedLayer(f"{bp}: pooling {raw!r} is not supported (max / average / last)")
+        hidden = bcfg.get("hidden_layers", []) or []
+        if any(str(l.get("name", "")).lower() == "parallel_branches" for l in hidden):
+            raise UnsupportedLayer(f"{bp}: a nested parallel_branches is not supported")
+        layers, width = _block(hidden, bp, cin, use_masking_default, DROP_TAPS, frames=frames)
+        if width % 4:
+            raise UnsupportedLayer(f"{bp}: a branch of {width} channels (a multiple of 4: a lane of the pool kernel owns four)")
+        branches.append(Branch(layers, _POOLINGS[raw], width))
+    if merge != "concat" and len({b.channels for b in branches}) != 1:
+        # keras.layers.Add / Average / Maximum: "Inputs have incompatible shapes"
+        raise ValueError(f"{p}: parallel_branches merge {merge!r} over branches of unequal width "
+                         f"{[b.channels for b in branches]} (Inputs have incompatible shapes)")
+    node = ParallelBranches(p, merge, branches)
+    if node.channels > BRANCHES_MAX_WIDTH:
+        raise UnsupportedLayer(f"{p}: parallel_branches leaves {node.channels} channels (up to {BRANCHES_MAX_WIDTH}: the width of "
+                               "the vector slot the pool kernels fill and the dense kernels read)")
+    return node
 
 
 def resolve_string_processor(model_cfg: dict) -> dict:
@@ -747,11 +858,21 @@ def build_plan(model_cfg: dict) -> ModelPlan:
     nmd_dims: list[int] = []
     rep_cfg = model_cfg["representation_learner"]
     frames = int((emb.get("input_shape") or [None])[0] or emb.get("frames", 6))   # the graph input is input_shape (builder.py:846)
-    rep, rep_c = _block(rep_cfg.get("hidden_layers", []), "rep", e, use_masking, nmd_dims, frames=frames)
-    pooling = str(rep_cfg.get("pooling", "")).lower()
-    pooling = {"masked_max": "max", "masked_average": "average"}.get(pooling, pooling)
-    if pooling not in ("max", "average"):
-        raise UnsupportedLayer(f"pooling {pooling!r} is not supported (max / average only)")
+    hidden = rep_cfg.get("hidden_layers", [])
+    # a parallel_branches of pooled branches closes the block with `pooling: null`, and _build_block then returns the tensor
+    # alone (builder.py:1169-1193): the taps in front of the branches are dropped too, the model has no nmd output
+    closes = any(str(l.get("name", "")).lower() == "parallel_branches" for l in hidden)
+    rep, rep_c = _block(hidden, "rep", e, use_masking, DROP_TAPS if closes else nmd_dims, frames=frames)
+    if rep and isinstance(rep[-1], ParallelBranches):
+        if rep_cfg.get("pooling") is not None:
+            raise ValueError(f"representation_learner.pooling {rep_cfg.get('pooling')!r} behind a parallel_branches of pooled "
+                             "branches: the poolers take a (B, frames, L, C) tensor, the merge leaves (B, C) - pooling must be null")
+        pooling = None
+    else:
+        pooling = str(rep_cfg.get("pooling", "")).lower()
+        if pooling not in _POOLINGS:
+            raise UnsupportedLayer(f"pooling {pooling!r} is not supported (max / average / last)")
+        pooling = _POOLINGS[pooling]
     cls, n_cls = _block(model_cfg["classifier"].get("hidden_layers", []), "classifier", rep_c,
                         use_masking, None)
     plan = ModelPlan(vocab=sp["vocab_size"], embedding_dim=e, rep=rep, pooling=pooling,
@@ -861,6 +982,16 @@ def _build_strand_plan(model_cfg: dict, sp: dict, graph_input: str, branched: li
                      strands=strands, merge=merge)
 
 
+def flat_layers(seq):
+    """The layers of ``seq`` with every ``parallel_branches`` replaced by its branches' layers, in branch order."""
+    for layer in seq:
+        if isinstance(layer, ParallelBranches):
+            for b in layer.branches:
+                yield from flat_layers(b.layers)
+        else:
+            yield layer
+
+
 def weight_shapes(plan: ModelPlan) -> dict[str, tuple]:
     """Canonical variable names -> shapes."""
     out: dict[str, tuple] = {}
@@ -882,7 +1013,7 @@ def weight_shapes(plan: ModelPlan) -> dict[str, tuple]:
             out[f"{c.name}/bias"] = (c.filters,)
 
     for seq in (plan.rep, plan.classifier, plan.reliability or []):
-        for layer in seq:
+        for layer in flat_layers(seq):
             if isinstance(layer, Conv):
                 conv(layer)
             elif isinstance(layer, Norm):
@@ -1021,7 +1152,7 @@ def frame_attn_flops_per_position(plan: ModelPlan) -> list[tuple[str, int, int]]
     per POSITION (six tokens): q/k/v and output projections 4 x 2 C^2, feed-forward 2 x 2 C F, per token; scores and
     context 2 x 2 x 6 x 6 x C per position."""
     rows = []
-    for layer in plan.rep:
+    for layer in flat_layers(plan.rep):
         if isinstance(layer, FrameAttn):
             c, f = layer.channels, layer.ff_dim
             rows.append((layer.name, 6 * (8 * c * c + 4 * c * f), 4 * 36 * c))
@@ -1031,7 +1162,7 @@ def frame_attn_flops_per_position(plan: ModelPlan) -> list[tuple[str, int, int]]
 def conv_flops_per_position(plan: ModelPlan) -> list[tuple[str, int, int, int, str, int]]:
     """(name, k, cin, cout, padding, stride) of every conv, in execution order."""
     rows = []
-    for layer in plan.rep:
+    for layer in flat_layers(plan.rep):
         if isinstance(layer, Conv):
             rows.append((layer.name, layer.kernel_size, layer.cin, layer.filters, layer.padding, layer.strides))
         elif isinstance(layer, ResBlock):

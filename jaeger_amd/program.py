@@ -24,6 +24,10 @@ conv launches with epilogue stages:
   ``2 * units`` channels; the mask kept, or dropped with ``ignore_mask``
 * ``multi_scale_conv -> norm -> activation``                  one mask op (the AND of the branches' output masks) and one
   multi-scale conv op (``layers.py:1433-1595``), out of place: every branch's conv, bias and activation and the concat / add
+* ``parallel_branches`` of pooled branches                    per branch its layers by the same walk, on the trunk's tensor and
+  mask, and one pool-and-merge op (``builder.py:1109-1153``): max / average / last pool of the branch's tensor, stored at
+  the branch's offset (concat) or added / maximised into the vector (sum / average / max; average scales on its last branch)
+* ``pooling: last``                                           one pool-and-merge op (``layers.py:541-578``)
 
 Pure host logic (numpy + ctypes structs): unit-tested on CPU.
 """
@@ -35,7 +39,7 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 from . import _lib as L
-from .plan import HYENA_PE_DIM, Act, AxialAttn, BiLstm, Conv, Dense, FrameAttn, Hyena, LengthAttn, LocalAttn, ModelPlan, MultiScaleConv, Nmd, Norm, ResBlock, UnsupportedLayer, weight_shapes
+from .plan import HYENA_PE_DIM, Act, AxialAttn, BiLstm, Conv, Dense, FrameAttn, Hyena, LengthAttn, LocalAttn, ModelPlan, MultiScaleConv, Nmd, Norm, ParallelBranches, ResBlock, UnsupportedLayer, flat_layers, weight_shapes
 
 _ACT_CODE = {None: L.ACT_NONE, "linear": L.ACT_NONE, "gelu": L.ACT_GELU_TANH, "gelu_erf": L.ACT_GELU_ERF,
              "relu": L.ACT_RELU, "tanh": L.ACT_TANH, "sigmoid": L.ACT_SIGMOID}
@@ -75,6 +79,7 @@ class _Slots:
     def __init__(self, n: int, what: str):
         self.free = list(range(n))
         self.what = what
+        self.held: set[int] = set()          # slots that stay taken whoever gives them back (a trunk's, while its branches run)
 
     def take(self) -> int:
         if not self.free:
@@ -82,7 +87,7 @@ class _Slots:
         return self.free.pop(0)
 
     def give(self, s: int) -> None:
-        if s is not None and s >= 0 and s not in self.free:
+        if s is not None and s >= 0 and s not in self.free and s not in self.held:
             self.free.append(s)
             self.free.sort()
 
@@ -318,14 +323,16 @@ class Program:
                         + (f" heads={op.k} ff={op.arg}" if op.kind == L.OP_LENGTHATTN else "")
                         + (f" order={op.k} flags={op.arg} table_rows={op.stride}" if op.kind == L.OP_HYENA else "")
                         + (f" units={op.k} ignore_mask={op.arg & L.BILSTM_IGNORE_MASK}" if op.kind == L.OP_BILSTM else "")
-                        + (f" branches={op.k} merge={'add' if op.arg == L.MSCONV_ADD else 'concat'}" if op.kind in (L.OP_MSCONV, L.OP_MSMASK) else ""))
+                        + (f" branches={op.k} merge={'add' if op.arg == L.MSCONV_ADD else 'concat'}" if op.kind in (L.OP_MSCONV, L.OP_MSMASK) else "")
+                        + (f" pool={('max', 'average', '?', 'last')[op.arg & 3]} merge={('store', 'add', 'max')[op.k % 3]} "
+                           f"vec={op.out_vec}[{op.vec_off}:{op.vec_off + op.cout}] scale={op.f0:g}" if op.kind == L.OP_POOLVEC else ""))
         return rows
 
 
 class _Compiler:
     def __init__(self, plan: ModelPlan, weights: dict[str, np.ndarray]):
         self.plan, self.w = plan, weights
-        for layer in plan.rep:                  # (optional: the stored positional encoding of a layer with seq_len is used when it is there)
+        for layer in flat_layers(plan.rep):     # (optional: the stored positional encoding of a layer with seq_len is used when it is there)
             pe = f"{layer.name}/hyena/filter/pos_encoding" if isinstance(layer, Hyena) else None
             if pe in weights and layer.seq_len is not None and tuple(weights[pe].shape) != (layer.seq_len, HYENA_PE_DIM):
                 raise ValueError(f"weight {pe}: shape {tuple(weights[pe].shape)} != expected ({layer.seq_len}, {HYENA_PE_DIM}) "
@@ -570,6 +577,68 @@ class _Compiler:
             self._emit_conv(ident, buf, L.JG_BUF_NONE, stages, om, out)
             self._flush_nmd(pending, out)
             buf, mask = out, om2
+        buf, mask = self._walk(layers, i, buf, mask, plan.embedding_dim)
+        if buf == L.JG_BUF_IDS:
+            raise UnsupportedLayer("the representation learner has no conv layer")
+        if plan.pooling is None:                 # a parallel_branches of pooled branches wrote the embedding vector itself
+            if buf is not None:
+                raise UnsupportedLayer("pooling: null needs a parallel_branches of pooled branches as the last layer")
+            return
+        if buf is None:
+            raise ValueError("a pooling behind a parallel_branches of pooled branches (the merge leaves a vector)")
+        if plan.pooling == "last":
+            self._pool_vec(buf, mask, "last", plan.rep_channels, 0, L.POOLVEC_STORE, 1.0, "pooling: last")
+            return
+        # max1d / average1d: the stock Keras Global*Pooling1D of a strand branch (builder.py:1706-1707) - no mask, no sentinel
+        kind = L.POOL_MAX if plan.pooling in ("max", "max1d") else L.POOL_AVG      # (without a mask: plain max / mean)
+        if plan.pooling in ("max1d", "average1d"):
+            mask = L.JG_BUF_NONE
+        self.ops.append(self._op(L.OP_POOL, in_buf=buf, in_mask=mask, out_vec=L.VEC_EMBEDDING, vec_off=0,
+                                 cout=plan.rep_channels, arg=kind))
+
+    def _pool_vec(self, buf: int, mask: int, pooling: str, channels: int, vec_off: int, merge: int, scale: float, what: str):
+        """One pool-and-merge op: ``pooling`` of ``buf`` under ``mask`` into the embedding vector at ``vec_off``."""
+        if pooling == "last":
+            self._refuse_unmasked_reader(f"{what} (MaskedLastPooling reads position count - 1 of a row whatever its mask says)")
+        kind = {"max": L.POOL_MAX, "average": L.POOL_AVG, "last": L.POOL_LAST}[pooling]
+        self.ops.append(self._op(L.OP_POOLVEC, in_buf=buf, in_mask=mask, out_vec=L.VEC_EMBEDDING, vec_off=vec_off, cout=channels,
+                                 arg=kind, k=merge, f0=scale))
+
+    def _branches(self, layer: ParallelBranches, buf: int, mask: int, channels: int):
+        """The branches of a ``parallel_branches`` on the trunk's tensor ``buf`` under ``mask``: the trunk's two slots stay
+        taken while the branches run, every branch starts from the trunk's dead-position state, and its pooled vector meets
+        the embedding vector by the layer's merge - in branch order, which fixes the float32 sum."""
+        if buf == L.JG_BUF_IDS:
+            raise UnsupportedLayer(f"{layer.name}: parallel_branches directly on the embedding is not supported")
+        dead = (self.dead_margin, self.dead_layer)
+        held = [(slots, s) for slots, s in ((self.bufs, buf), (self.masks, mask)) if s >= 0 and s not in slots.held]
+        for slots, s in held:
+            slots.held.add(s)
+        n, off = len(layer.branches), 0
+        for b, branch in enumerate(layer.branches):
+            self.dead_margin, self.dead_layer = dead
+            bbuf, bmask = self._walk(branch.layers, 0, buf, mask, channels)
+            if bbuf is None:
+                raise UnsupportedLayer(f"{layer.name}: a nested parallel_branches is not supported")
+            if layer.merge == "concat":
+                merge, scale = L.POOLVEC_STORE, 1.0
+            else:
+                merge = L.POOLVEC_STORE if b == 0 else L.POOLVEC_MAX if layer.merge == "max" else L.POOLVEC_ADD
+                scale = 1.0 / n if layer.merge == "average" and b == n - 1 else 1.0
+            self._pool_vec(bbuf, bmask, branch.pooling, branch.channels, off, merge, scale,
+                           f"{layer.name}/branch{b}: pooling: last")
+            off += branch.channels if layer.merge == "concat" else 0
+            self.bufs.give(bbuf)                 # (the trunk's own slots are held: a branch without layers gives nothing back)
+            self.masks.give(bmask)
+        self.dead_margin, self.dead_layer = dead
+        for slots, s in held:
+            slots.held.discard(s)
+            slots.give(s)
+
+    def _walk(self, layers: list, i: int, buf: int, mask: int, cin: int):
+        """The layer walk from ``layers[i]`` on: the tensor in slot ``buf`` (``cin`` channels) under mask slot ``mask`` through
+        the layers; returns the output slot and the mask slot behind them - or (None, None) behind a ``parallel_branches``,
+        which leaves the embedding vector.  The trunk and every branch of a ``parallel_branches`` go through this."""
         while i < len(layers):
             layer = layers[i]
             pending: list = []
@@ -639,13 +708,16 @@ class _Compiler:
             elif isinstance(layer, (Norm, Act)):
                 if buf == L.JG_BUF_IDS:
                     raise UnsupportedLayer("a norm / activation directly on the embedding is not supported")
+                if buf in self.bufs.held:
+                    raise UnsupportedLayer(f"{getattr(layer, 'name', layer.__class__.__name__)}: a norm / activation as the first layer of "
+                                           "a branch is not supported (it runs in place, on the tensor the other branches read)")
                 stages: list = []
                 i, mask2 = self._fuse_tail(layers, i, stages, mask, 0, pending)
                 if pending:
                     raise UnsupportedLayer("an nmd layer must directly follow a conv or residual block")
                 if not stages:
                     raise UnsupportedLayer(f"{getattr(layer, 'name', layer)}: unsupported standalone layer")
-                channels = self._channels_before(layers, i)
+                channels = self._channels_before(layers, i, cin)
                 # a LayerNorm must lead its op (the LayerNorm kernel): cut the list in front of every LN stage
                 cuts = [0] + [j for j, st in enumerate(stages) if st.kind == L.ST_LN and j > 0] + [len(stages)]
                 for a_, b_ in zip(cuts[:-1], cuts[1:]):
@@ -765,21 +837,19 @@ class _Compiler:
                 if mask2 != mask:
                     self.masks.give(mask)
                 mask = mask2
+            elif isinstance(layer, ParallelBranches):
+                if i + 1 != len(layers):
+                    raise UnsupportedLayer(f"{layer.name}: a layer behind a parallel_branches of pooled branches")
+                self._branches(layer, buf, mask, self._channels_before(layers, i, cin))
+                return None, None
             elif isinstance(layer, Nmd):
                 raise UnsupportedLayer("an nmd layer must directly follow a conv or residual block")
             else:
                 raise UnsupportedLayer(f"layer {layer!r} is not supported in the representation learner")
-        if buf == L.JG_BUF_IDS:
-            raise UnsupportedLayer("the representation learner has no conv layer")
-        # max1d / average1d: the stock Keras Global*Pooling1D of a strand branch (builder.py:1706-1707) - no mask, no sentinel
-        kind = L.POOL_MAX if plan.pooling in ("max", "max1d") else L.POOL_AVG      # (without a mask: plain max / mean)
-        if plan.pooling in ("max1d", "average1d"):
-            mask = L.JG_BUF_NONE
-        self.ops.append(self._op(L.OP_POOL, in_buf=buf, in_mask=mask, out_vec=L.VEC_EMBEDDING, vec_off=0,
-                                 cout=plan.rep_channels, arg=kind))
+        return buf, mask
 
-    def _channels_before(self, layers, i) -> int:
-        c = self.plan.embedding_dim
+    def _channels_before(self, layers, i, cin: int) -> int:
+        c = cin
         for layer in layers[:i]:
             if isinstance(layer, Conv):
                 c = layer.filters

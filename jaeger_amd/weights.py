@@ -17,7 +17,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .plan import AxialAttn, BiLstm, Conv, Dense, FrameAttn, Hyena, LengthAttn, LocalAttn, ModelPlan, MultiScaleConv, Nmd, Norm, ResBlock, weight_shapes
+from .plan import AxialAttn, BiLstm, Conv, Dense, FrameAttn, Hyena, LengthAttn, LocalAttn, ModelPlan, MultiScaleConv, Nmd, Norm, ParallelBranches, ResBlock, weight_shapes
 
 
 def random_weights(plan: ModelPlan, seed: int = 38341) -> dict[str, np.ndarray]:
@@ -73,9 +73,10 @@ def load_npz(path) -> dict[str, np.ndarray]:
 
 def attention_layers(plan: ModelPlan) -> list[str]:
     """Names of the plan's cross_frame_attention, local_attention, transformer_encoder, axial_attention, hyena_block,
-    masked_bilstm and multi_scale_conv layers: the ones with nested sub-layers, whose weights load from ``.npz`` only."""
+    masked_bilstm, multi_scale_conv and parallel_branches layers: the ones with nested sub-layers, whose weights load from
+    ``.npz`` only."""
     return [l.name for seq in (plan.rep, plan.classifier, plan.reliability or []) for l in seq
-            if isinstance(l, (FrameAttn, LocalAttn, LengthAttn, AxialAttn, Hyena, BiLstm, MultiScaleConv))]
+            if isinstance(l, (FrameAttn, LocalAttn, LengthAttn, AxialAttn, Hyena, BiLstm, MultiScaleConv, ParallelBranches))]
 
 
 def attention_kinds(plan: ModelPlan) -> str:
@@ -84,7 +85,7 @@ def attention_kinds(plan: ModelPlan) -> str:
     kinds = [name for cls, name in ((FrameAttn, "cross_frame_attention"), (LocalAttn, "local_attention"),
                                           (LengthAttn, "transformer_encoder"), (AxialAttn, "axial_attention"),
                                           (Hyena, "hyena_block"), (BiLstm, "masked_bilstm"),
-                                          (MultiScaleConv, "multi_scale_conv"))
+                                          (MultiScaleConv, "multi_scale_conv"), (ParallelBranches, "parallel_branches"))
              if any(isinstance(l, cls) for l in layers)]
     return " / ".join(kinds)
 
@@ -97,13 +98,13 @@ def _refuse_attention(plan: ModelPlan, what: str, source) -> None:
     """The Keras-3 ``.weights.h5`` and SavedModel-bundle loaders map weight groups onto plan layers by order and shapes.
     A MultiHeadAttention nests four EinsumDense sub-layers - a HyenaBlock an operator, a filter generator and its
     Sequential filter networks, a MaskedBiLSTM a Bidirectional wrapper around two LSTM layers and their cells, a
-    MultiScaleConv1D a list of MaskedConv1D branches - whose key
+    MultiScaleConv1D a list of MaskedConv1D branches, a parallel_branches entry one sub-graph per branch - whose key
     scheme in either container could only be guessed here (no checkpoint of such a model and no Keras to write one): a
     guessed scheme would be untestable, so both loaders refuse such a plan and name the route that works."""
     names = attention_layers(plan)
     if names:
         raise AttentionWeightsUnsupported(
-            f"{source}: the {what} loader does not map the nested sub-layer variables (MultiHeadAttention, HyenaOperator, Bidirectional, MaskedConv1D branches) of "
+            f"{source}: the {what} loader does not map the nested sub-layer variables (MultiHeadAttention, HyenaOperator, Bidirectional, MaskedConv1D branches, parallel_branches blocks) of "
             f"{attention_kinds(plan)} layers ({', '.join(names)}); {NPZ_ROUTE}")
 
 
