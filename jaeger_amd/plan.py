@@ -6,8 +6,8 @@ in ``nnlib/builder.py`` (``build_fragment_classifier`` :442-838,
 :1697-1714).  This module resolves the same section into a flat, fully
 defaulted plan (every default below cites the constructor it comes from) that
 ``program.py`` compiles for the MI355X engine.  Layers outside the conv family
-(gated pooling ...) raise :class:`UnsupportedLayer`; the attention layers, ``hyena_block``, ``masked_bilstm``,
-``multi_scale_conv`` and ``parallel_branches`` are plan nodes of their own.
+(gated pooling ...) raise :class:`UnsupportedLayer`; the row-mixer kinds are plan nodes of their own, one class per kind
+in ``mixers.py`` (``MIXERS``: YAML name -> class), and so is ``parallel_branches``.
 
 Canonical weight names (shared with the loaders in ``weights.py``):
 ``embedding/embeddings``; ``rep/<i>/{kernel,bias,gamma,beta,moving_mean,
@@ -27,38 +27,11 @@ from dataclasses import dataclass, field
 from typing import Any
 
 from . import maps
+from .mixers import *  # noqa: F401,F403 - the mixer classes, Conv, Norm, UnsupportedLayer and the kernels' limits: part of this module's interface
 
 _ACT_ALIASES = ("relu", "gelu", "sigmoid", "softmax", "tanh")
 _NORMS = ("masked_batchnorm", "masked_dyt", "masked_layernorm")
 _DEFAULT_SIGNALS = ["max_prob", "entropy", "energy", "margin", "nmd_norm"]
-
-
-class UnsupportedLayer(ValueError):
-    """A layer / option of the project YAML that the MI355X engine does not implement."""
-
-
-@dataclass
-class Conv:
-    name: str                      # weight prefix
-    kernel_size: int
-    cin: int
-    filters: int
-    strides: int = 1               # layers.py:1154
-    padding: str = "valid"         # layers.py:1156 (MaskedConv1D default!)
-    dilation_rate: int = 1         # layers.py:1157
-    use_bias: bool = True          # layers.py:1159
-    activation: str | None = None  # layers.py:1158
-    use_masking: bool = True       # layers.py:1163
-    mask_mode: str = "any"         # layers.py:1164
-
-
-@dataclass
-class Norm:
-    name: str
-    kind: str                      # masked_batchnorm | masked_dyt | masked_layernorm
-    channels: int
-    epsilon: float = 1e-5          # MaskedBatchNorm layers.py:804; LN 1e-3 layers.py:306
-    use_masking: bool = True
 
 
 @dataclass
@@ -95,255 +68,6 @@ class Dense:
     units: int
     use_bias: bool = True
     activation: str | None = None
-
-
-@dataclass
-class FrameAttn:
-    """One CrossFrameAttention layer (layers.py:2283-2384): at every position the six frames are six tokens of
-    ``channels``: pre-LN (eps 1e-6, :2321-2323) -> MultiHeadAttention(num_heads, key_dim = channels // num_heads,
-    :2324-2330) over the frames -> residual (:2367); with ``use_ffn`` LN -> Dense(ff_dim, gelu) -> Dense(channels) ->
-    residual (:2370-2376).  The layer does not set supports_masking: no mask leaves it."""
-    name: str
-    channels: int
-    heads: int
-    key_dim: int
-    ff_dim: int
-    use_ffn: bool = True           # layers.py:2310
-
-
-@dataclass(frozen=True)
-class AttnKernel:
-    """What one of the attention kernels covers, where they differ."""
-    channels: tuple
-    ff_optional: bool              # feed_forward_dim 0 (no feed-forward half) is allowed
-    max_half: int | None           # the largest half-window, None: no window
-
-
-ATTN_KEY_DIMS = (4, 8, 16, 32, 64)
-ATTN_MAX_FF = 256
-LOCALATTN_MAX_HALF = 32
-LENGTHATTN_CHANNELS = (16, 32, 64)
-LENGTHATTN_MAX_FF = ATTN_MAX_FF
-FRAMEATTN = AttnKernel((32, 64), True, None)                             # csrc/jg_frameattn.hip
-LOCALATTN = AttnKernel((16, 32, 64), False, LOCALATTN_MAX_HALF)          # csrc/jg_localattn.hip
-LENGTHATTN = AttnKernel(LENGTHATTN_CHANNELS, False, None)               # csrc/jg_lengthattn.hip
-
-
-def attn_limit(kernel: AttnKernel, channels: int, heads: int, ff_dim: int, half_window: int = 0) -> str | None:
-    """Why the attention kernel cannot run this size, or None."""
-    if channels not in kernel.channels:
-        return f"embed_dim {channels} (the kernel covers {' / '.join(map(str, kernel.channels))} channels)"
-    if heads < 1 or channels % heads or channels // heads not in ATTN_KEY_DIMS:
-        return (f"num_heads {heads} at embed_dim {channels} (key_dim = embed_dim / num_heads must be one of "
-                f"{', '.join(map(str, ATTN_KEY_DIMS))})")
-    if (ff_dim or not kernel.ff_optional) and (ff_dim % 16 or not 16 <= ff_dim <= ATTN_MAX_FF):
-        return f"feed_forward_dim {ff_dim} (a multiple of 16 up to {ATTN_MAX_FF})"
-    if kernel.max_half is not None and not 0 <= half_window <= kernel.max_half:
-        return (f"window_size {2 * half_window} or more (the kernel covers half-windows of 0 to {kernel.max_half} "
-                f"positions, window_size up to {2 * kernel.max_half + 1})")
-    return None
-
-
-@dataclass
-class LocalAttn:
-    """One LocalAttention layer (layers.py:2520-2645): windowed self-attention along the length axis inside every frame
-    row, ``blocks`` times: pre-LN (eps 1e-6, :2556-2558) -> MultiHeadAttention(num_heads, key_dim = channels //
-    num_heads, :2559-2564) under the mask ``|q - k| <= half_window and mask[k]`` (:2579-2585, :2604-2609) -> residual
-    (:2619); LN -> Dense(ff_dim, gelu) -> Dense(channels) -> residual (:2621-2623), always present.  The layer sets
-    supports_masking and ``compute_mask`` returns the mask (:2550, :2627-2628): the mask stays behind it."""
-    name: str
-    channels: int
-    heads: int
-    key_dim: int
-    ff_dim: int
-    half_window: int               # window_size // 2 (:2581)
-    blocks: int = 1                # num_blocks (:2538)
-
-
-_LOCALATTN_REQUIRED = ("embed_dim", "num_heads", "feed_forward_dim", "window_size")   # no defaults (layers.py:2531-2537)
-
-
-@dataclass
-class LengthAttn:
-    """One stand-alone TransformerEncoder layer (layers.py:2206-2280) with ``attention_axes = 2``: full self-attention
-    along the length axis inside every frame row - pre-LN (eps 1e-6, :2224-2226) -> MultiHeadAttention(num_heads, key_dim
-    = channels // num_heads, :2227-2233) under Keras 3's implicit query / value masks -> residual (:2256); LN ->
-    Dense(ff_dim, gelu) -> Dense(channels) -> residual (:2259-2264).  The layer does not set supports_masking: no mask
-    leaves it."""
-    name: str
-    channels: int
-    heads: int
-    key_dim: int
-    ff_dim: int
-
-
-@dataclass
-class AxialAttn:
-    """One AxialAttention layer (layers.py:2400-2517): per block a TransformerEncoder along the length (:2461-2470), a
-    CrossFrameAttention with its feed-forward half (:2474-2483), the post norm and the residual add of the block's input
-    (:2485-2501).  Only block 0's encoder sees the layer's incoming mask; ``masked_layernorm`` / ``masked_dyt`` post norms
-    get it in every block (:2495-2496).  The layer sets supports_masking (:2442): the mask stays behind it."""
-    name: str
-    channels: int
-    heads: int
-    key_dim: int
-    ff_dim: int
-    blocks: int = 1                # num_blocks (:2426)
-    norm_type: str = "layernorm"   # :2428 (layernorm | masked_layernorm | masked_dyt | masked_batchnorm)
-    epsilon: float = 1e-6          # of the post norm only (:2427); the encoders' layer norms have 1e-6 hard-coded
-    alpha_init: float = 0.5        # MaskedDYT's initial alpha (:2429): training only, the weights carry alpha
-
-    def post_norm(self, block: int) -> Norm:
-        """The post norm of block ``block`` as a :class:`Norm` (``layernorm`` has masked_layernorm's variables)."""
-        kind = "masked_layernorm" if self.norm_type == "layernorm" else self.norm_type
-        return Norm(f"{self.name}/block{block}/post_norm", kind, self.channels, self.epsilon, True)
-
-    def length(self, block: int) -> LengthAttn:
-        return LengthAttn(f"{self.name}/block{block}/length", self.channels, self.heads, self.key_dim, self.ff_dim)
-
-    def frame(self, block: int) -> FrameAttn:
-        return FrameAttn(f"{self.name}/block{block}/frame", self.channels, self.heads, self.key_dim, self.ff_dim, True)
-
-
-_ATTN_REQUIRED = ("embed_dim", "num_heads", "feed_forward_dim")                    # no defaults (layers.py:2207-2212, :2420-2425)
-# the constructors' own arguments plus what keras.layers.Layer.__init__ takes: any other key is an unknown keyword there
-_AXIAL_KEYS = {"embed_dim", "num_heads", "feed_forward_dim", "dropout_rate", "num_blocks", "epsilon", "norm_type",
-               "alpha_init", "name", "dtype", "trainable"}
-_ENCODER_KEYS = {"embed_dim", "num_heads", "feed_forward_dim", "dropout_rate", "attention_axes", "name", "dtype", "trainable"}
-AXIAL_NORM_TYPES = ("layernorm", "masked_layernorm", "masked_dyt", "masked_batchnorm")
-
-
-@dataclass
-class Hyena:
-    """One HyenaBlock (layers.py:3023-3153) on the rows of the (frames, length, channels) tensor: ``x * m`` -> LayerNorm
-    (eps 1e-6, :3075) ``* m`` -> HyenaOperator (:2937-3002: ``order + 1`` bias-free projections, ``order`` gated causal long
-    convolutions whose filters come from HyenaFilter, :2766-2915) -> with ``output_projection`` Dense(channels) -> plus the
-    masked input, ``* m`` (:3103-3133).  The layer sets supports_masking (:3072): the mask stays behind it, and masked
-    positions are exact zeros."""
-    name: str
-    channels: int
-    order: int = 2                 # :3051
-    filter_hidden: int = 32        # :3052
-    filter_layers: int = 2         # :3053
-    filter_activation: str | None = "gelu"   # :3054
-    filter_normalize: bool = False # :3057
-    output_projection: bool = False   # :3056
-    seq_len: int | None = None     # :3050: rows of the stored positional encoding; a longer call fails in the reference
-
-
-#: what the hyena kernels (csrc/jg_hyena.hip) and the host's filter table (program.py) cover
-HYENA_CHANNELS = (16, 32, 64)
-HYENA_MAX_ORDER = 4
-HYENA_PE_DIM = 16                  # HyenaFilter's pe_dim default (:2797); HyenaOperator never passes another
-HYENA_ACTIVATIONS = ("gelu", "sin", "relu", "tanh", "sigmoid", "silu", "swish", "linear")
-# the constructor's own arguments (:3047-3059) plus what keras.layers.Layer.__init__ takes; kernel_regularizer_w is the
-# builder's spelling of the regulariser's weight
-_HYENA_KEYS = {"dim", "seq_len", "order", "filter_hidden", "filter_layers", "filter_activation", "dropout",
-               "output_projection", "filter_normalize", "kernel_regularizer", "kernel_regularizer_w", "name", "dtype",
-               "trainable"}
-
-
-def hyena_limit(channels: int, order: int, filter_layers: int, activation) -> str | None:
-    """Why the hyena kernels / the host's filter table cannot run this layer, or None."""
-    if channels not in HYENA_CHANNELS:
-        return f"dim {channels} (the kernels cover {' / '.join(map(str, HYENA_CHANNELS))} channels)"
-    if not 1 <= order <= HYENA_MAX_ORDER:
-        return f"order {order} (the kernels cover orders 1 to {HYENA_MAX_ORDER})"
-    if filter_layers < 1:
-        return f"filter_layers {filter_layers} (the filter network needs at least one Dense layer)"
-    if activation is not None and str(activation).lower() not in HYENA_ACTIVATIONS:
-        return (f"filter_activation {activation!r} (the host tables the filter with one of "
-                f"{', '.join(HYENA_ACTIVATIONS)} or none)")
-    return None
-
-
-@dataclass
-class BiLstm:
-    """One MaskedBiLSTM (layers.py:1335-1430) on the rows of the (frames, length, channels) tensor: Keras 3
-    ``Bidirectional(LSTM(units, return_sequences=True), merge_mode="concat")`` under the incoming mask - a masked step keeps
-    both states and repeats the direction's previous output (zeros while no valid step has come) - or, with ``ignore_mask``,
-    under none.  ``compute_mask`` returns the mask, or None with ``ignore_mask`` (:1405-1410)."""
-    name: str
-    cin: int
-    units: int
-    ignore_mask: bool = False      # :1361
-
-    @property
-    def channels(self) -> int:
-        """What the layer leaves: the two directions side by side."""
-        return 2 * self.units
-
-
-#: what the kernel (csrc/jg_bilstm.hip) covers
-BILSTM_UNITS = (16, 32, 64)
-BILSTM_MAX_CHANNELS = 128
-# the constructor's own arguments (:1354-1363) plus what keras.layers.Layer.__init__ takes
-_BILSTM_KEYS = {"units", "dropout", "recurrent_dropout", "return_sequences", "use_cudnn", "ignore_mask", "name", "dtype",
-                "trainable"}
-
-
-def bilstm_limit(channels: int, units: int) -> str | None:
-    """Why the bilstm kernel cannot run this layer, or None."""
-    if units not in BILSTM_UNITS:
-        return f"units {units} (the kernel covers {' / '.join(map(str, BILSTM_UNITS))} units)"
-    if channels % 16 or not 16 <= channels <= BILSTM_MAX_CHANNELS:
-        return f"{channels} incoming channels (a multiple of 16 up to {BILSTM_MAX_CHANNELS})"
-    return None
-
-
-@dataclass
-class MultiScaleConv:
-    """One MultiScaleConv1D (layers.py:1433-1595): ``len(branches)`` MaskedConv1Ds over the same rows of the (frames, length,
-    channels) tensor, every one with padding "same" and strides 1 (:1504-1505, :1517-1526) and its own kernel_size,
-    dilation_rate, activation, use_bias and mask_mode; their outputs concatenated along the channels (``merge`` "concat") or
-    summed in branch order (``merge`` "add", tf.add_n; :1539-1542).  The mask behind the layer is the AND of the branches'
-    output masks (:1544-1548), none where the branches do not mask or no mask arrives."""
-    name: str
-    cin: int
-    merge: str                     # "concat" | "add" (:1448)
-    branches: list                 # list[Conv], named <name>/branch<b>
-
-    @property
-    def channels(self) -> int:
-        """What the layer leaves: the branches side by side, or their common width."""
-        return sum(b.filters for b in self.branches) if self.merge == "concat" else self.branches[0].filters
-
-    @property
-    def use_masking(self) -> bool:
-        return self.branches[0].use_masking
-
-
-#: what the kernel (csrc/jg_msconv.hip) covers
-MSCONV_MAX_BRANCHES = 4
-MSCONV_MAX_CHANNELS = 128
-MSCONV_MAX_KERNEL = 15
-MSCONV_MAX_SPAN = 64
-# the constructor's own arguments (:1445-1453); the last three matter in training only
-_MSCONV_KEYS = {"branches", "merge", "use_bias", "kernel_initializer", "kernel_regularizer", "kernel_regularizer_w"}
-# MaskedConv1D's arguments (:1150-1168) a branch entry may carry
-_MSCONV_BRANCH_KEYS = {"filters", "kernel_size", "strides", "padding", "dilation_rate", "activation", "use_bias",
-                       "kernel_initializer", "bias_initializer", "kernel_regularizer", "axis",
-                       "use_masking", "mask_mode", "name", "dtype", "trainable"}
-
-
-def msconv_limit(cin: int, merge: str, branches: list) -> str | None:
-    """Why the multi-scale conv kernel cannot run this layer, or None."""
-    if cin % 16 or not 16 <= cin <= MSCONV_MAX_CHANNELS:
-        return f"{cin} incoming channels (a multiple of 16 up to {MSCONV_MAX_CHANNELS})"
-    if not 1 <= len(branches) <= MSCONV_MAX_BRANCHES:
-        return f"{len(branches)} branches (the kernel covers 1 to {MSCONV_MAX_BRANCHES})"
-    for b, c in enumerate(branches):
-        if c.filters % 8 or not 8 <= c.filters <= MSCONV_MAX_CHANNELS:
-            return f"branch {b}: filters {c.filters} (a multiple of 8 up to {MSCONV_MAX_CHANNELS})"
-        if not 1 <= c.kernel_size <= MSCONV_MAX_KERNEL:
-            return f"branch {b}: kernel_size {c.kernel_size} (the kernel covers 1 to {MSCONV_MAX_KERNEL})"
-        if c.dilation_rate < 1 or (c.kernel_size - 1) * c.dilation_rate > MSCONV_MAX_SPAN:
-            return (f"branch {b}: (kernel_size - 1) x dilation_rate = {(c.kernel_size - 1) * c.dilation_rate} "
-                    f"(dilation_rate at least 1, the product up to {MSCONV_MAX_SPAN})")
-    cout = sum(c.filters for c in branches) if merge == "concat" else branches[0].filters
-    if cout % 16 or not 16 <= cout <= MSCONV_MAX_CHANNELS:
-        return f"{cout} output channels (a multiple of 16 up to {MSCONV_MAX_CHANNELS})"
-    return None
 
 
 @dataclass
@@ -388,12 +112,6 @@ class _DropTaps:
 
 
 DROP_TAPS = _DropTaps()
-
-
-def _constructor_accepts(cfg: dict, keys: set) -> bool:
-    """Whether the reference's constructor would take this config: the three required arguments are there and no key is
-    an unknown keyword (keras.layers.Layer.__init__ raises on one)."""
-    return all(k in cfg for k in _ATTN_REQUIRED) and not set(cfg) - keys
 
 
 @dataclass
@@ -544,179 +262,15 @@ def _block(layers: list[dict], prefix: str, cin: int, use_masking_default: bool,
             cin = int(cfg["units"])
         elif name == "dropout":
             continue                                            # identity at inference
-        elif name == "cross_frame_attention":
-            # builder.py:1155: CrossFrameAttention(**config) (embed_dim, num_heads, feed_forward_dim, dropout_rate, use_ffn);
-            # :1165-1166: previous_channels = embed_dim
-            if frames is None:
-                raise UnsupportedLayer(f"{p}: cross_frame_attention needs the (frames, length, channels) tensor of the "
-                                       "representation learner: not supported in a head or on a strand branch")
-            if frames != 6:
-                raise UnsupportedLayer(f"{p}: cross_frame_attention over {frames} frames (the kernel attends over the six "
-                                       "reading frames of a translated window)")
-            c, h = int(cfg["embed_dim"]), int(cfg["num_heads"])
-            use_ffn = bool(cfg.get("use_ffn", True))
-            f = int(cfg["feed_forward_dim"]) if use_ffn else 0
-            if c != cin:
-                raise UnsupportedLayer(f"{p}: embed_dim {c} != {cin} incoming channels (the layer's residual adds them, "
-                                       "layers.py:2367)")
-            why = attn_limit(FRAMEATTN, c, h, f)
-            if why is not None:
-                raise UnsupportedLayer(f"{p}: cross_frame_attention with {why}")
-            out.append(FrameAttn(p, c, h, c // h, f, use_ffn))
-        elif name == "local_attention" and all(k in cfg for k in _LOCALATTN_REQUIRED):
-            # builder.py:290, :1155: LocalAttention(**config) (embed_dim, num_heads, feed_forward_dim, window_size,
-            # dropout_rate, num_blocks); an entry without one of the four required arguments raises in the reference's
-            # constructor and falls through to the generic refusal below
-            if frames is None:
-                raise UnsupportedLayer(f"{p}: local_attention needs the (frames, length, channels) tensor of the "
-                                       "representation learner: not supported in a head or on a strand branch")
-            c, h, f = int(cfg["embed_dim"]), int(cfg["num_heads"]), int(cfg["feed_forward_dim"])
-            window, blocks = int(cfg["window_size"]), int(cfg.get("num_blocks", 1))
-            if window < 1:
-                raise UnsupportedLayer(f"{p}: local_attention window_size {window} (must be positive, layers.py:2542-2543)")
-            if blocks < 1:
-                raise UnsupportedLayer(f"{p}: local_attention num_blocks {blocks} (at least one block)")
-            if c != cin:
-                raise UnsupportedLayer(f"{p}: embed_dim {c} != {cin} incoming channels (the layer's residual adds them, "
-                                       "layers.py:2619)")
-            why = attn_limit(LOCALATTN, c, h, f, window // 2)
-            if why is not None:
-                raise UnsupportedLayer(f"{p}: local_attention with {why}")
-            out.append(LocalAttn(p, c, h, c // h, f, window // 2, blocks))
-        elif (name == "transformer_encoder" and _constructor_accepts(cfg, _ENCODER_KEYS)) or \
-                (name == "axial_attention" and _constructor_accepts(cfg, _AXIAL_KEYS)):
-            # builder.py:1155: TransformerEncoder(**config) / AxialAttention(**config); an entry the constructor would not
-            # take (a required argument missing, an unknown keyword) falls through to the generic refusal below
-            if frames is None:
-                raise UnsupportedLayer(f"{p}: {name} needs the (frames, length, channels) tensor of the "
-                                       "representation learner: not supported in a head or on a strand branch")
-            c, h, f = int(cfg["embed_dim"]), int(cfg["num_heads"]), int(cfg["feed_forward_dim"])
-            if c != cin:
-                raise UnsupportedLayer(f"{p}: embed_dim {c} != {cin} incoming channels (the layer's residual adds them, "
-                                       "layers.py:2256)")
-            why = attn_limit(LENGTHATTN, c, h, f)
-            if why is not None:
-                raise UnsupportedLayer(f"{p}: {name} with {why}")
-            if name == "transformer_encoder":
-                axes = cfg.get("attention_axes", 2)
-                if axes != 2 and list(axes if isinstance(axes, (list, tuple)) else [axes]) != [2]:
-                    raise UnsupportedLayer(f"{p}: transformer_encoder attention_axes {axes!r} (the kernel attends along the "
-                                           "length axis, attention_axes = 2)")
-                out.append(LengthAttn(p, c, h, c // h, f))
-            else:
-                if frames != 6:
-                    raise UnsupportedLayer(f"{p}: axial_attention over {frames} frames (its frame half attends over the six "
-                                           "reading frames of a translated window)")
-                blocks = int(cfg.get("num_blocks", 1))
-                if blocks < 1:
-                    raise UnsupportedLayer(f"{p}: axial_attention num_blocks {blocks} (at least one block)")
-                nt = str(cfg.get("norm_type", "layernorm")).lower()
-                nt = "layernorm" if nt == "layer_normalization" else nt          # layers.py:2449
-                if nt not in AXIAL_NORM_TYPES:
-                    raise UnsupportedLayer(f"{p}: axial_attention norm_type {nt!r} (layers.py:2457 raises: one of "
-                                           f"{', '.join(AXIAL_NORM_TYPES)})")
-                why = attn_limit(FRAMEATTN, c, h, f)
-                if why is not None:
-                    raise UnsupportedLayer(f"{p}: axial_attention with {why} (its frame half)")
-                out.append(AxialAttn(p, c, h, c // h, f, blocks, nt, float(cfg.get("epsilon", 1e-6)),
-                                     float(cfg.get("alpha_init", 0.5))))
-        elif name == "hyena_block" and "dim" in cfg and not set(cfg) - _HYENA_KEYS:
-            # builder.py:1155: HyenaBlock(**config); an entry without `dim` or with an unknown keyword raises in the reference's
-            # constructor and falls through to the generic refusal below.  dropout and the regulariser matter in training only
-            if frames is None:
-                raise UnsupportedLayer(f"{p}: hyena_block needs the (frames, length, channels) tensor of the "
-                                       "representation learner: not supported in a head or on a strand branch")
-            c, order = int(cfg["dim"]), int(cfg.get("order", 2))
-            if c != cin:
-                raise UnsupportedLayer(f"{p}: dim {c} != {cin} incoming channels (the layer's residual adds them, "
-                                       "layers.py:3129)")
-            fl, act = int(cfg.get("filter_layers", 2)), cfg.get("filter_activation", "gelu")
-            why = hyena_limit(c, order, fl, act)
-            if why is not None:
-                raise UnsupportedLayer(f"{p}: hyena_block with {why}")
-            seq_len = cfg.get("seq_len")
-            if seq_len is not None and int(seq_len) < 1:
-                raise UnsupportedLayer(f"{p}: hyena_block seq_len {seq_len} (a positive number of positions, or none)")
+        elif name in MIXERS and MIXERS[name].accepts(cfg):
+            # a row mixer (mixers.py); an entry the reference's constructor would not take falls through to the generic
+            # refusal below
+            out.append(MIXERS[name].parse(p, cfg, cin, frames))
             nxt = layers[i + 1] if i + 1 < len(layers) else {}
-            if not drop and (str(nxt.get("name", "")).lower() == "nmd" or (nxt.get("config") or {}).get("return_nmd")):
-                raise UnsupportedLayer(f"{p}: an nmd tap directly behind hyena_block is not supported "
+            if MIXERS[name].tap_lookahead and not drop and \
+                    (str(nxt.get("name", "")).lower() == "nmd" or (nxt.get("config") or {}).get("return_nmd")):
+                raise UnsupportedLayer(f"{p}: an nmd tap directly behind {name} is not supported "
                                        "(the op's store carries no partial sums)")
-            out.append(Hyena(p, c, order, int(cfg.get("filter_hidden", 32)), fl,
-                             None if act is None or str(act).lower() == "linear" else str(act).lower(),
-                             bool(cfg.get("filter_normalize", False)), bool(cfg.get("output_projection", False)),
-                             None if seq_len is None else int(seq_len)))
-        elif name == "masked_bilstm" and "units" in cfg and not set(cfg) - _BILSTM_KEYS:
-            # builder.py:282, :1155: MaskedBiLSTM(**config); an entry without `units` or with an unknown keyword raises in the
-            # reference's constructor and falls through to the generic refusal below.  dropout / recurrent_dropout matter in
-            # training only, use_cudnn changes no formula
-            if frames is None:
-                raise UnsupportedLayer(f"{p}: masked_bilstm needs the (frames, length, channels) tensor of the "
-                                       "representation learner: not supported in a head or on a strand branch")
-            if not bool(cfg.get("return_sequences", True)):
-                raise UnsupportedLayer(f"{p}: masked_bilstm with return_sequences: false (the tensor loses its length axis, "
-                                       "and no layer behind it here takes a (frames, channels) tensor)")
-            units = int(cfg["units"])
-            why = bilstm_limit(cin, units)
-            if why is not None:
-                raise UnsupportedLayer(f"{p}: masked_bilstm with {why}")
-            nxt = layers[i + 1] if i + 1 < len(layers) else {}
-            if not drop and (str(nxt.get("name", "")).lower() == "nmd" or (nxt.get("config") or {}).get("return_nmd")):
-                raise UnsupportedLayer(f"{p}: an nmd tap directly behind masked_bilstm is not supported "
-                                       "(the op's store carries no partial sums)")
-            out.append(BiLstm(p, cin, units, bool(cfg.get("ignore_mask", False))))
-            cin = 2 * units
-        elif name == "multi_scale_conv" and "branches" in cfg and not set(cfg) - _MSCONV_KEYS:
-            # builder.py:277-304, :1155: MultiScaleConv1D(**config); an entry without `branches` or with a key that is none of
-            # the constructor's arguments raises there and falls through to the generic refusal below.  The initialiser and
-            # the regulariser matter in training only
-            branches, merge = cfg["branches"], cfg.get("merge", "concat")
-            if not isinstance(branches, list) or len(branches) == 0 or not all(isinstance(b, dict) for b in branches):
-                raise ValueError(f"{p}: branches must be a non-empty list of dicts")                      # :1456-1459
-            if merge not in ("concat", "add"):
-                raise ValueError(f"{p}: merge must be 'concat' or 'add', got {merge!r}")                 # :1460-1461
-            if merge == "add" and len({b.get("filters") for b in branches}) != 1:
-                raise ValueError(f"{p}: All branches must have the same filters when merge='add'")        # :1495-1500
-            convs = []
-            for b, bcfg in enumerate(branches):
-                pad, strides = bcfg.get("padding", "same"), bcfg.get("strides", 1)                       # :1504-1505
-                if str(pad).lower() != "same":
-                    raise ValueError(f"{p}: Branch {b}: padding must be 'same' to keep sequence length aligned across "
-                                     f"branches, got {pad!r}")                                            # :1517-1521
-                if strides != 1:
-                    raise ValueError(f"{p}: Branch {b}: strides must be 1 to keep sequence length aligned across "
-                                     f"branches, got {strides!r}")                                        # :1522-1526
-                mode = bcfg.get("mask_mode", "any")
-                if mode not in ("any", "majority", "strict"):
-                    raise ValueError(f"{p}: Branch {b}: Invalid mask_mode: {mode!r} (use 'any', 'majority' or 'strict')")   # :1170-1173
-                if set(bcfg) - _MSCONV_BRANCH_KEYS:
-                    raise UnsupportedLayer(f"{p}: branch {b}: {sorted(set(bcfg) - _MSCONV_BRANCH_KEYS)} are no arguments of "
-                                           "MaskedConv1D (layers.py:1148-1165)")
-                if bcfg.get("axis", -1) != -1:
-                    raise UnsupportedLayer(f"{p}: branch {b}: axis {bcfg['axis']!r} (the kernel convolves along the length axis "
-                                           "with the channels last, axis = -1)")
-                # use_bias defaults to the layer's (:1515); use_masking to MaskedConv1D's own True (:1161): builder.py:1019-1020
-                # injects the model-level use_masking for masked_conv1d / masked_batchnorm / residual_block entries only
-                convs.append(Conv(f"{p}/branch{b}", int(bcfg["kernel_size"]), cin, int(bcfg["filters"]), 1, "same",
-                                  int(bcfg.get("dilation_rate", 1)), bool(bcfg.get("use_bias", cfg.get("use_bias", True))),
-                                  bcfg.get("activation"), bool(bcfg.get("use_masking", True)), mode))
-            if frames is None:
-                raise UnsupportedLayer(f"{p}: multi_scale_conv needs the (frames, length, channels) tensor of the "
-                                       "representation learner: not supported in a head or on a strand branch")
-            if len({c.use_masking for c in convs}) != 1:
-                raise UnsupportedLayer(f"{p}: multi_scale_conv whose branches disagree on use_masking (the reference ANDs a "
-                                       "branch's mask with None there, layers.py:1544-1548)")
-            why = msconv_limit(cin, merge, convs)
-            if why is not None:
-                raise UnsupportedLayer(f"{p}: multi_scale_conv with {why}")
-            nxt = layers[i + 1] if i + 1 < len(layers) else {}
-            if not drop and (str(nxt.get("name", "")).lower() == "nmd" or (nxt.get("config") or {}).get("return_nmd")):
-                raise UnsupportedLayer(f"{p}: an nmd tap directly behind multi_scale_conv is not supported "
-                                       "(the op's store carries no partial sums)")
-            # builder.py:1161-1166 does not update previous_channels behind this layer (the entry has no top-level `filters`),
-            # so a residual_block that follows is constructed with a stale `shape` (:1075-1087).  That argument reaches
-            # ResidualBlockStack.__init__ as `in_shape` and is never read (layers.py:2658-2692, :2716-2721): the blocks build
-            # from the tensor they are called on.  The graph is the same, so such a block is accepted
-            out.append(MultiScaleConv(p, cin, merge, convs))
             cin = out[-1].channels
         elif name == "parallel_branches":
             out.append(_parallel_branches(p, cfg, cin, use_masking_default, nmd_dims, frames))
@@ -1000,13 +554,6 @@ def weight_shapes(plan: ModelPlan) -> dict[str, tuple]:
     elif plan.embedding_kind == "onehot_dense":
         out["embedding/kernel"] = (plan.vocab - 1, plan.embedding_dim)      # Dense(E, use_bias=False) on one-hot rows
 
-    def norm(n: Norm):
-        vars_ = {"masked_batchnorm": ("gamma", "beta", "moving_mean", "moving_variance"),
-                 "masked_dyt": ("alpha", "gamma", "beta"),
-                 "masked_layernorm": ("gamma", "beta")}[n.kind]
-        for v in vars_:
-            out[f"{n.name}/{v}"] = (1,) if v == "alpha" else (n.channels,)
-
     def conv(c: Conv):
         out[f"{c.name}/kernel"] = (c.kernel_size, c.cin, c.filters)
         if c.use_bias:
@@ -1017,7 +564,7 @@ def weight_shapes(plan: ModelPlan) -> dict[str, tuple]:
             if isinstance(layer, Conv):
                 conv(layer)
             elif isinstance(layer, Norm):
-                norm(layer)
+                out.update(norm_weight_shapes(layer))
             elif isinstance(layer, Nmd):
                 out[f"{layer.name}/moving_mean"] = (layer.channels,)
             elif isinstance(layer, ResBlock):
@@ -1026,124 +573,18 @@ def weight_shapes(plan: ModelPlan) -> dict[str, tuple]:
                         conv(c)
                 for n in (layer.bn1, layer.bn2, layer.bn3):
                     if n is not None:
-                        norm(n)
+                        out.update(norm_weight_shapes(n))
             elif isinstance(layer, Dense):
                 out[f"{layer.name}/kernel"] = (layer.cin, layer.units)
                 if layer.use_bias:
                     out[f"{layer.name}/bias"] = (layer.units,)
-            elif isinstance(layer, FrameAttn):
-                out.update(frame_attn_weight_shapes(layer))
-            elif isinstance(layer, LocalAttn):
-                out.update(local_attn_weight_shapes(layer))
-            elif isinstance(layer, LengthAttn):
-                out.update(length_attn_weight_shapes(layer))
-            elif isinstance(layer, Hyena):
-                out.update(hyena_weight_shapes(layer))
-            elif isinstance(layer, BiLstm):
-                out.update(bilstm_weight_shapes(layer))
-            elif isinstance(layer, MultiScaleConv):
-                out.update(msconv_weight_shapes(layer))
-            elif isinstance(layer, AxialAttn):
-                for j in range(layer.blocks):
-                    out.update(length_attn_weight_shapes(layer.length(j)))
-                    out.update(frame_attn_weight_shapes(layer.frame(j)))
-                    norm(layer.post_norm(j))
+            elif isinstance(layer, Mixer):
+                out.update(layer.weight_shapes())
         if seq is plan.rep and plan.nmd_merge_mode != "concat":                 # NMDMerge is built behind the rep block's layers
             for i, d in enumerate(plan.nmd_dims):
                 out[f"rep/nmd_merge/proj_{i}/kernel"] = (d, plan.nmd_merge_dim)
             if plan.nmd_merge_mode == "weighted":
                 out["rep/nmd_merge/layer_weights"] = (len(plan.nmd_dims),)
-    return out
-
-
-def frame_attn_weight_shapes(a: FrameAttn) -> dict[str, tuple]:
-    """Keras variable shapes of one CrossFrameAttention layer: LayerNormalization gamma / beta (C); MultiHeadAttention
-    query / key / value EinsumDense kernels (C, H, D) with biases (H, D), attention_output kernel (H, D, C) with bias (C);
-    the two Dense layers of the feed-forward half."""
-    c, h, d, f = a.channels, a.heads, a.key_dim, a.ff_dim
-    out = {f"{a.name}/attn_norm/gamma": (c,), f"{a.name}/attn_norm/beta": (c,)}
-    for part in ("query", "key", "value"):
-        out[f"{a.name}/mha/{part}/kernel"] = (c, h, d)
-        out[f"{a.name}/mha/{part}/bias"] = (h, d)
-    out[f"{a.name}/mha/attention_output/kernel"] = (h, d, c)
-    out[f"{a.name}/mha/attention_output/bias"] = (c,)
-    if a.use_ffn:
-        out.update({f"{a.name}/ffn_norm/gamma": (c,), f"{a.name}/ffn_norm/beta": (c,),
-                    f"{a.name}/ffn_dense1/kernel": (c, f), f"{a.name}/ffn_dense1/bias": (f,),
-                    f"{a.name}/ffn_dense2/kernel": (f, c), f"{a.name}/ffn_dense2/bias": (c,)})
-    return out
-
-
-def local_attn_weight_shapes(a: LocalAttn) -> dict[str, tuple]:
-    """Keras variable shapes of one LocalAttention layer, per block ``<name>/block<j>/``: the two LayerNormalization
-    layers' gamma / beta (C); MultiHeadAttention query / key / value EinsumDense kernels (C, H, D) with biases (H, D),
-    attention_output kernel (H, D, C) with bias (C); the two Dense layers of the feed-forward half."""
-    c, h, d, f = a.channels, a.heads, a.key_dim, a.ff_dim
-    out: dict[str, tuple] = {}
-    for j in range(a.blocks):
-        b = f"{a.name}/block{j}"
-        out.update({f"{b}/ln1/gamma": (c,), f"{b}/ln1/beta": (c,)})
-        for part in ("query", "key", "value"):
-            out[f"{b}/mha/{part}/kernel"] = (c, h, d)
-            out[f"{b}/mha/{part}/bias"] = (h, d)
-        out[f"{b}/mha/attention_output/kernel"] = (h, d, c)
-        out[f"{b}/mha/attention_output/bias"] = (c,)
-        out.update({f"{b}/ln2/gamma": (c,), f"{b}/ln2/beta": (c,), f"{b}/ffn1/kernel": (c, f), f"{b}/ffn1/bias": (f,),
-                    f"{b}/ffn2/kernel": (f, c), f"{b}/ffn2/bias": (c,)})
-    return out
-
-
-def length_attn_weight_shapes(a: LengthAttn) -> dict[str, tuple]:
-    """Keras variable shapes of one TransformerEncoder: the leaf names and shapes of a CrossFrameAttention layer with its
-    feed-forward half (the two classes hold the same sub-layers under the same names, layers.py:2224-2245, :2321-2345)."""
-    return frame_attn_weight_shapes(FrameAttn(a.name, a.channels, a.heads, a.key_dim, a.ff_dim, True))
-
-
-def hyena_weight_shapes(a: Hyena) -> dict[str, tuple]:
-    """Keras variable shapes of one HyenaBlock: the LayerNormalization's gamma / beta (C); the operator's ``order + 1``
-    bias-free projections (C, C); per order the filter network's Dense layers (16 -> filter_hidden ... -> C, the last one
-    alone with ``filter_layers`` 1) and the window's ``alphas`` / ``biases`` (order, C); the output projection if there is
-    one.  ``<name>/hyena/filter/pos_encoding`` (seq_len, 16) is optional and not listed: when the weights hold it the
-    filter table uses its rows (program.py: hyena_filter_tables)."""
-    c, n = a.channels, a.name
-    out: dict[str, tuple] = {f"{n}/norm/gamma": (c,), f"{n}/norm/beta": (c,)}
-    for k in range(a.order + 1):
-        out[f"{n}/hyena/proj_{k}/kernel"] = (c, c)
-    for o in range(a.order):
-        cin = HYENA_PE_DIM
-        for j in range(a.filter_layers):
-            units = c if j == a.filter_layers - 1 else a.filter_hidden
-            out[f"{n}/hyena/filter/ffn_{o}/dense_{j}/kernel"] = (cin, units)
-            out[f"{n}/hyena/filter/ffn_{o}/dense_{j}/bias"] = (units,)
-            cin = units
-    out[f"{n}/hyena/filter/alphas"] = (a.order, c)
-    out[f"{n}/hyena/filter/biases"] = (a.order, c)
-    if a.output_projection:
-        out[f"{n}/out_proj/kernel"] = (c, c)
-        out[f"{n}/out_proj/bias"] = (c,)
-    return out
-
-
-def bilstm_weight_shapes(a: BiLstm) -> dict[str, tuple]:
-    """Keras variable shapes of one MaskedBiLSTM: per direction (``layer.bilstm.forward_layer.cell`` /
-    ``backward_layer.cell``) the LSTMCell's kernel (C, 4U), recurrent_kernel (U, 4U) and bias (4U), the 4U columns in the
-    gate order i, f, g, o."""
-    out: dict[str, tuple] = {}
-    for d in ("forward", "backward"):
-        out[f"{a.name}/{d}/kernel"] = (a.cin, 4 * a.units)
-        out[f"{a.name}/{d}/recurrent_kernel"] = (a.units, 4 * a.units)
-        out[f"{a.name}/{d}/bias"] = (4 * a.units,)
-    return out
-
-
-def msconv_weight_shapes(a: MultiScaleConv) -> dict[str, tuple]:
-    """Keras variable shapes of one MultiScaleConv1D: per branch (``layer._convs[b]``, a MaskedConv1D) the kernel
-    (kernel_size, cin, filters) and, with use_bias, the bias (filters)."""
-    out: dict[str, tuple] = {}
-    for c in a.branches:
-        out[f"{c.name}/kernel"] = (c.kernel_size, c.cin, c.filters)
-        if c.use_bias:
-            out[f"{c.name}/bias"] = (c.filters,)
     return out
 
 

@@ -19,7 +19,7 @@ conv launches with epilogue stages:
   frame-attention op and an element-wise op with the post norm and the add of the block's input
   (``layers.py:2400-2517``); the mask kept; the norm / activation ride the last block's element-wise op
 * ``hyena_block -> norm -> activation``                       one hyena op (``layers.py:2724-3153``), out of place, the mask
-  kept; its implicit filters are tabled here once (:func:`hyena_filter_tables`) and travel in the weight blob
+  kept; its implicit filters are tabled on the host once (:func:`hyena_filter_tables`) and travel in the weight blob
 * ``masked_bilstm -> norm -> activation``                     one bilstm op (``layers.py:1335-1430``), out of place, rows of
   ``2 * units`` channels; the mask kept, or dropped with ``ignore_mask``
 * ``multi_scale_conv -> norm -> activation``                  one mask op (the AND of the branches' output masks) and one
@@ -29,7 +29,7 @@ conv launches with epilogue stages:
   the branch's offset (concat) or added / maximised into the vector (sum / average / max; average scales on its last branch)
 * ``pooling: last``                                           one pool-and-merge op (``layers.py:541-578``)
 
-Pure host logic (numpy + ctypes structs): unit-tested on CPU.
+The row mixers' ops: ``emit`` of the kind's class in ``mixers.py``.  Pure host logic (numpy + ctypes structs): unit-tested on CPU.
 """
 
 from __future__ import annotations
@@ -39,19 +39,11 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 from . import _lib as L
-from .plan import HYENA_PE_DIM, Act, AxialAttn, BiLstm, Conv, Dense, FrameAttn, Hyena, LengthAttn, LocalAttn, ModelPlan, MultiScaleConv, Nmd, Norm, ParallelBranches, ResBlock, UnsupportedLayer, flat_layers, weight_shapes
+from .mixers import (_MASK_MODE, POSITION_ROWS, Mixer, act_code,  # noqa: F401 - the last three: importable from here
+                     hyena_filter_tables, hyena_table_rows, unpack_msconv_descriptor)
+from .plan import Act, Conv, Dense, ModelPlan, Nmd, Norm, ParallelBranches, ResBlock, UnsupportedLayer, flat_layers, weight_shapes
 
-_ACT_CODE = {None: L.ACT_NONE, "linear": L.ACT_NONE, "gelu": L.ACT_GELU_TANH, "gelu_erf": L.ACT_GELU_ERF,
-             "relu": L.ACT_RELU, "tanh": L.ACT_TANH, "sigmoid": L.ACT_SIGMOID}
-_MASK_MODE = {"any": L.MASK_ANY, "majority": L.MASK_MAJORITY, "strict": L.MASK_STRICT}
 _SIGNAL_CODE = {"max_prob": 1, "entropy": 2, "energy": 3, "margin": 4, "nmd_norm": 5}
-
-
-def act_code(name) -> int:
-    key = name.lower() if isinstance(name, str) else name
-    if key not in _ACT_CODE:
-        raise UnsupportedLayer(f"activation {name!r} is not supported by the MI355X engine")
-    return _ACT_CODE[key]
 
 
 class _Blob:
@@ -101,196 +93,17 @@ def pack_conv_kernel(kernel: np.ndarray) -> np.ndarray:
     return out
 
 
-FRAME_ATTN_EPSILON = 1e-6      # both LayerNormalization layers of CrossFrameAttention (layers.py:2321-2323, :2335-2337)
-
-
-def pack_frame_attn(a: FrameAttn, w: dict[str, np.ndarray]) -> np.ndarray:
-    """The weights of one CrossFrameAttention layer as the kernel reads them (csrc/jg_frameattn.hip), folded in float64:
-
-    * ``LN(x) @ W + b`` with ``LN(x) = n(x) * gamma + beta`` is ``n(x) @ (gamma[:, None] * W) + (beta @ W + b)``: the layer
-      norms' gamma / beta go into the q / k / v kernels and into ffn_dense1, the kernel normalises only;
-    * MultiHeadAttention multiplies the query by ``1 / sqrt(key_dim)`` behind its bias: into the query's kernel and bias.
-
-    Layout: ``JgAttnWeights`` (csrc/jg_mixer_dev.h), the one view the three attention kernels read the blob through -
-    wqkv | bqkv | wo | bo and, with a feed-forward half, w1 | b1 | w2 | b2."""
-    c, h, d = a.channels, a.heads, a.key_dim
-    f64 = lambda name: np.asarray(w[f"{a.name}/{name}"], np.float64)
-    g1, be1 = f64("attn_norm/gamma"), f64("attn_norm/beta")
-    parts_w, parts_b = [], []
-    for part, scale in (("query", 1.0 / np.sqrt(float(d))), ("key", 1.0), ("value", 1.0)):
-        kern = f64(f"mha/{part}/kernel").reshape(c, h * d)
-        bias = f64(f"mha/{part}/bias").reshape(h * d)
-        parts_w.append(g1[:, None] * kern * scale)
-        parts_b.append((be1 @ kern + bias) * scale)
-    out = [np.stack(parts_w), np.stack(parts_b), f64("mha/attention_output/kernel").reshape(h * d, c),
-           f64("mha/attention_output/bias")]
-    if a.use_ffn:
-        g2, be2 = f64("ffn_norm/gamma"), f64("ffn_norm/beta")
-        k1 = f64("ffn_dense1/kernel")
-        out += [g2[:, None] * k1, be2 @ k1 + f64("ffn_dense1/bias"), f64("ffn_dense2/kernel"), f64("ffn_dense2/bias")]
-    return np.concatenate([x.ravel() for x in out]).astype(np.float32)
-
-
-LOCAL_ATTN_EPSILON = 1e-6      # both LayerNormalization layers of a LocalAttention block (layers.py:2556-2558, :2565-2567)
-
-
-def pack_local_attn(a: LocalAttn, block: int, w: dict[str, np.ndarray]) -> np.ndarray:
-    """The weights of block ``block`` of a LocalAttention layer as the kernel reads them (csrc/jg_localattn.hip):
-    :func:`pack_frame_attn`'s fold and layout (``JgAttnWeights``, csrc/jg_mixer_dev.h) - ln1 / ln2 gamma and beta into the q / k / v kernels and into ffn1, the
-    query's ``1 / sqrt(key_dim)`` into its kernel and bias, in float64."""
-    p = f"{a.name}/block{block}"
-    leaf = {"ln1": "attn_norm", "ln2": "ffn_norm", "ffn1": "ffn_dense1", "ffn2": "ffn_dense2", "mha": "mha"}
-    renamed = {}
-    for name, v in w.items():
-        if name.startswith(p + "/"):
-            head, rest = name[len(p) + 1:].split("/", 1)
-            renamed[f"{p}/{leaf[head]}/{rest}"] = v
-    return pack_frame_attn(FrameAttn(p, a.channels, a.heads, a.key_dim, a.ff_dim, True), renamed)
-
-
-LENGTH_ATTN_EPSILON = 1e-6     # both LayerNormalization layers of a TransformerEncoder (layers.py:2224-2226, :2237-2239)
-
-
-def pack_length_attn(a: LengthAttn, w: dict[str, np.ndarray]) -> np.ndarray:
-    """The weights of one TransformerEncoder as the kernel reads them (csrc/jg_lengthattn.hip): :func:`pack_frame_attn`'s
-    fold and layout (``JgAttnWeights``, csrc/jg_mixer_dev.h) under the same leaf names."""
-    return pack_frame_attn(FrameAttn(a.name, a.channels, a.heads, a.key_dim, a.ff_dim, True), w)
-
-
-HYENA_EPSILON = 1e-6           # the LayerNormalization of a HyenaBlock (layers.py:3075)
-
-
-def hyena_position_rows(n_pos: int) -> np.ndarray:
-    """HyenaFilter._make_positional_encoding (layers.py:2871-2880) for positions 0 .. n_pos - 1 at pe_dim 16: the ARGUMENTS
-    ``pos * div`` as the reference forms them, float32 products of float32 factors (``div = exp(range(0, 16, 2) * -(log(10000)
-    / 16))``), their sine and cosine in float64; row ``[sin_0, cos_0, sin_1, cos_1, ...]``."""
-    f = np.float32
-    pos = np.arange(n_pos, dtype=f)[:, None]
-    div = np.exp(np.arange(0, HYENA_PE_DIM, 2, dtype=f) * f(-(np.log(f(10000.0)) / f(HYENA_PE_DIM)))).astype(f)
-    arg = (pos * div[None, :]).astype(f).astype(np.float64)
-    return np.stack([np.sin(arg), np.cos(arg)], axis=-1).reshape(n_pos, HYENA_PE_DIM)
-
-
-def _hyena_activation(name, x: np.ndarray) -> np.ndarray:
-    """HyenaFilter._hidden_activation (layers.py:2864-2869) in float64: "sin" is tf.sin, the others what Keras 3 resolves
-    the name to ("gelu": the tanh form)."""
-    if name is None or name == "linear":
-        return x
-    if name == "sin":
-        return np.sin(x)
-    if name == "gelu":
-        return 0.5 * x * (1.0 + np.tanh(np.sqrt(2.0 / np.pi) * (x + 0.044715 * x ** 3)))
-    if name == "relu":
-        return np.maximum(x, 0.0)
-    if name == "tanh":
-        return np.tanh(x)
-    if name == "sigmoid":
-        return 1.0 / (1.0 + np.exp(-x))
-    if name in ("silu", "swish"):
-        return x / (1.0 + np.exp(-x))
-    raise UnsupportedLayer(f"hyena filter_activation {name!r} cannot be evaluated on the host")
-
-
-def hyena_table_rows(a: Hyena) -> int:
-    """Rows of the layer's filter table: ``seq_len`` where the layer fixes it (the reference's stored positional encoding has
-    that many rows, a longer call fails there), else the position rows a program carries."""
-    return a.seq_len if a.seq_len is not None else POSITION_ROWS
-
-
-def hyena_filter_tables(a: Hyena, w: dict[str, np.ndarray], rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
-    """HyenaFilter.call (layers.py:2882-2915) for every position the program may meet, once:
-    ``h[i, t, :] = (exp(-|alpha_i| t) + bias_i) * FFN_i(PE[t])`` as float32 ``(order, rows, C)``, evaluated in float64 from the
-    positional rows (the stored ``<name>/hyena/filter/pos_encoding`` of a layer with ``seq_len`` if the weights hold it, else recomputed) - and the
-    running sum of its squares over ``t``, ``ssq[i, t, :] = sum over s <= t of h[i, s, :] ** 2`` (of the float32 table, summed
-    in float64): with ``filter_normalize`` a call at ``l`` positions divides channel ``c`` of filter ``i`` by
-    ``sqrt(ssq[i, l - 1, c])``, and by nothing where that is zero (divide_no_nan)."""
-    rows = hyena_table_rows(a) if rows is None else rows
-    # (without seq_len the reference stores one row and recomputes the encoding at every call, :2817, :2888-2891)
-    stored = w.get(f"{a.name}/hyena/filter/pos_encoding") if a.seq_len is not None else None
-    if stored is not None:
-        stored = np.asarray(stored, np.float64)
-        if stored.ndim != 2 or stored.shape[1] != HYENA_PE_DIM or stored.shape[0] < rows:
-            raise ValueError(f"weight {a.name}/hyena/filter/pos_encoding: shape {stored.shape} != expected ({rows}, {HYENA_PE_DIM})")
-        pe = stored[:rows]
-    else:
-        pe = hyena_position_rows(rows)
-    f64 = lambda name: np.asarray(w[f"{a.name}/hyena/filter/{name}"], np.float64)
-    alphas, biases = np.abs(f64("alphas")), f64("biases")
-    t = np.arange(rows, dtype=np.float64)[:, None]
-    h = np.empty((a.order, rows, a.channels), np.float32)
-    for i in range(a.order):
-        x = pe
-        for j in range(a.filter_layers):
-            x = x @ f64(f"ffn_{i}/dense_{j}/kernel") + f64(f"ffn_{i}/dense_{j}/bias")
-            if j < a.filter_layers - 1:
-                x = _hyena_activation(a.filter_activation, x)
-        h[i] = ((np.exp(-alphas[i][None, :] * t) + biases[i][None, :]) * x).astype(np.float32)
-    ssq = np.cumsum(h.astype(np.float64) ** 2, axis=1).astype(np.float32)
-    return h, ssq
-
-
-def pack_hyena(a: Hyena, w: dict[str, np.ndarray]) -> np.ndarray:
-    """The weights and tables of one HyenaBlock as the kernels read them (csrc/jg_hyena.hip), folded in float64:
-    ``(n(x) * gamma + beta) @ W_k`` is ``n(x) @ (gamma[:, None] * W_k) + beta @ W_k`` - the kernel normalises only, and
-    zeroes the projections of a masked position.  Layout: wp [order + 1][C][C] | bp [order + 1][C] | with
-    output_projection wo [C][C] | bo [C] | h [order][rows][C] | with filter_normalize ssq [order][rows][C]."""
-    f64 = lambda name: np.asarray(w[f"{a.name}/{name}"], np.float64)
-    gamma, beta = f64("norm/gamma"), f64("norm/beta")
-    kernels = [f64(f"hyena/proj_{k}/kernel") for k in range(a.order + 1)]
-    out = [np.stack([gamma[:, None] * k for k in kernels]), np.stack([beta @ k for k in kernels])]
-    if a.output_projection:
-        out += [f64("out_proj/kernel"), f64("out_proj/bias")]
-    h, ssq = hyena_filter_tables(a, w)
-    out.append(h)
-    if a.filter_normalize:
-        out.append(ssq)
-    return np.concatenate([np.asarray(x, np.float32).ravel() for x in out])
-
-
-def pack_bilstm(a: BiLstm, w: dict[str, np.ndarray]) -> np.ndarray:
-    """The weights of one MaskedBiLSTM as the kernel reads them (csrc/jg_bilstm.hip): per direction (forward, backward)
-    W [C][4U] | R [U][4U] | b [4U], the 4U columns permuted so that the four gates of one unit stand next to each other and
-    the units of one wave together - column ``64 w + 4 n + g`` holds Keras' column ``g U + 16 w + n`` (gate g of i, f, g, o;
-    unit 16 w + n).  Nothing is folded: the values pass through float64 and are rounded back unchanged."""
-    u = a.units
-    perm = np.arange(4 * u).reshape(4, u).T.ravel()                    # new column 4 unit + g <- old column g U + unit
-    out = []
-    for d in ("forward", "backward"):
-        f64 = lambda name: np.asarray(w[f"{a.name}/{d}/{name}"], np.float64)
-        out += [f64("kernel")[:, perm], f64("recurrent_kernel")[:, perm], f64("bias")[perm]]
-    return np.concatenate([x.ravel() for x in out]).astype(np.float32)
-
-
-def pack_msconv(a: MultiScaleConv, w: dict[str, np.ndarray]) -> np.ndarray:
-    """The blob of one MultiScaleConv1D as the two ops read it (csrc/jg_msconv.h): a descriptor of ``MSCONV_MAX_BRANCHES`` x
-    ``MSCONV_DESC_FIELDS`` int32 values stored as float32 BIT PATTERNS - per branch filters, taps, dilation, activation code,
-    mask mode, has-bias, channel offset in the output (0 for every branch under "add"), weight offset in floats from the
-    blob's start; unused branches zeros - then per branch the kernel ``[taps][cin][fpad]`` and the bias ``[fpad]``, fpad =
-    filters rounded up to 16, the padding columns and an absent bias zeros.  Nothing is folded."""
-    n = L.MSCONV_MAX_BRANCHES * L.MSCONV_DESC_FIELDS
-    desc = np.zeros((L.MSCONV_MAX_BRANCHES, L.MSCONV_DESC_FIELDS), np.int32)
-    parts, at, ch = [], n, 0
-    for b, c in enumerate(a.branches):
-        fpad = (c.filters + 15) // 16 * 16
-        kern = np.zeros((c.kernel_size, c.cin, fpad), np.float32)
-        kern[:, :, :c.filters] = np.asarray(w[f"{c.name}/kernel"], np.float32)
-        bias = np.zeros(fpad, np.float32)
-        if c.use_bias:
-            bias[:c.filters] = np.asarray(w[f"{c.name}/bias"], np.float32)
-        desc[b] = (c.filters, c.kernel_size, c.dilation_rate, act_code(c.activation), _MASK_MODE[c.mask_mode], int(c.use_bias),
-                   ch if a.merge == "concat" else 0, at)
-        parts += [kern.ravel(), bias]
-        at += kern.size + fpad
-        ch += c.filters
-    return np.concatenate([desc.ravel().view(np.float32)] + parts)
-
-
-def unpack_msconv_descriptor(blob: np.ndarray, n_branches: int) -> list[dict]:
-    """The descriptor at the head of a :func:`pack_msconv` blob, back as one dict per branch."""
-    fields = ("filters", "taps", "dilation", "activation", "mask_mode", "has_bias", "channel_offset", "weight_offset")
-    n = L.MSCONV_MAX_BRANCHES * L.MSCONV_DESC_FIELDS
-    desc = np.ascontiguousarray(blob[:n], np.float32).view(np.int32).reshape(L.MSCONV_MAX_BRANCHES, L.MSCONV_DESC_FIELDS)
-    return [dict(zip(fields, map(int, desc[b]))) for b in range(n_branches)]
+#: op kind -> what ``Program.describe`` adds behind the fields every op has
+_DESCRIBE = {
+    L.OP_FRAMEATTN: lambda op: f" heads={op.k} ff={op.arg}",
+    L.OP_LOCALATTN: lambda op: f" heads={op.k} ff={op.arg} half_window={op.stride}",
+    L.OP_HYENA: lambda op: f" order={op.k} flags={op.arg} table_rows={op.stride}",
+    L.OP_BILSTM: lambda op: f" units={op.k} ignore_mask={op.arg & L.BILSTM_IGNORE_MASK}",
+    L.OP_MSCONV: lambda op: f" branches={op.k} merge={'add' if op.arg == L.MSCONV_ADD else 'concat'}",
+    L.OP_POOLVEC: lambda op: (f" pool={('max', 'average', '?', 'last')[op.arg & 3]} merge={('store', 'add', 'max')[op.k % 3]} "
+                              f"vec={op.out_vec}[{op.vec_off}:{op.vec_off + op.cout}] scale={op.f0:g}"),
+}
+_DESCRIBE.update({L.OP_LENGTHATTN: _DESCRIBE[L.OP_FRAMEATTN], L.OP_MSMASK: _DESCRIBE[L.OP_MSCONV]})
 
 
 @dataclass
@@ -318,25 +131,15 @@ class Program:
             st = "+".join(stk[op.stages[s].kind] for s in range(op.n_stages))
             rows.append(f"{kinds[op.kind][3:]:9s} in={op.in_buf} out={op.out_buf} m={op.in_mask}->{op.out_mask} "
                         f"k={op.k} c={op.cin}->{op.cout} s={op.stride} d={op.dilation} [{st}]"
-                        + (f" heads={op.k} ff={op.arg}" if op.kind == L.OP_FRAMEATTN else "")
-                        + (f" heads={op.k} ff={op.arg} half_window={op.stride}" if op.kind == L.OP_LOCALATTN else "")
-                        + (f" heads={op.k} ff={op.arg}" if op.kind == L.OP_LENGTHATTN else "")
-                        + (f" order={op.k} flags={op.arg} table_rows={op.stride}" if op.kind == L.OP_HYENA else "")
-                        + (f" units={op.k} ignore_mask={op.arg & L.BILSTM_IGNORE_MASK}" if op.kind == L.OP_BILSTM else "")
-                        + (f" branches={op.k} merge={'add' if op.arg == L.MSCONV_ADD else 'concat'}" if op.kind in (L.OP_MSCONV, L.OP_MSMASK) else "")
-                        + (f" pool={('max', 'average', '?', 'last')[op.arg & 3]} merge={('store', 'add', 'max')[op.k % 3]} "
-                           f"vec={op.out_vec}[{op.vec_off}:{op.vec_off + op.cout}] scale={op.f0:g}" if op.kind == L.OP_POOLVEC else ""))
+                        + _DESCRIBE.get(op.kind, lambda op: "")(op))
         return rows
 
 
 class _Compiler:
     def __init__(self, plan: ModelPlan, weights: dict[str, np.ndarray]):
         self.plan, self.w = plan, weights
-        for layer in flat_layers(plan.rep):     # (optional: the stored positional encoding of a layer with seq_len is used when it is there)
-            pe = f"{layer.name}/hyena/filter/pos_encoding" if isinstance(layer, Hyena) else None
-            if pe in weights and layer.seq_len is not None and tuple(weights[pe].shape) != (layer.seq_len, HYENA_PE_DIM):
-                raise ValueError(f"weight {pe}: shape {tuple(weights[pe].shape)} != expected ({layer.seq_len}, {HYENA_PE_DIM}) "
-                                 "(HyenaFilter stores the rows of its seq_len only)")
+        for layer in flat_layers(plan.rep):     # (a kind's optional variables; weight_shapes covers the others)
+            getattr(layer, "check_weights", lambda w: None)(weights)
         missing = [n for n in weight_shapes(plan) if n not in weights]
         if missing:
             raise KeyError(f"weights missing for: {missing[:6]}{'...' if len(missing) > 6 else ''}")
@@ -479,16 +282,6 @@ class _Compiler:
                                    "leaves zeros at positions whose band holds no valid key, where the Keras graph holds "
                                    "values that depend on its version and precision")
 
-    def _frame_op(self, a: FrameAttn, in_buf: int, out_buf: int):
-        return self._op(L.OP_FRAMEATTN, in_buf=in_buf, out_buf=out_buf, in_mask=L.JG_BUF_NONE, out_mask=L.JG_BUF_NONE,
-                        k=a.heads, cin=a.channels, cout=a.channels, arg=a.ff_dim if a.use_ffn else 0,
-                        f0=FRAME_ATTN_EPSILON, w_off=self.blob.add(pack_frame_attn(a, self.w)))
-
-    def _length_op(self, a: LengthAttn, in_buf: int, out_buf: int, in_mask: int, out_mask: int):
-        return self._op(L.OP_LENGTHATTN, in_buf=in_buf, out_buf=out_buf, in_mask=in_mask, out_mask=out_mask, k=a.heads,
-                        cin=a.channels, cout=a.channels, arg=a.ff_dim, f0=LENGTH_ATTN_EPSILON,
-                        w_off=self.blob.add(pack_length_attn(a, self.w)))
-
     def _emit_mixer(self, layers: list, i: int, what: str, buf: int, mask: int, out_mask: int, build_ops: list):
         """A row-mixer layer (frame / local / length attention, hyena, bilstm, multi-scale conv) at ``layers[i]``: its ops - ``build_ops``, one
         ``(in_buf, out_buf) -> op`` per op, each into a fresh slot, never in place - with the bias / batch norm / unmasked
@@ -553,13 +346,9 @@ class _Compiler:
                 pos = dict(w_off=self.blob.add(pe), k=POSITION_ROWS)
             self.ops.append(self._op(L.OP_EMBED, out_buf=buf, out_mask=mask, cout=plan.embedding_dim, b_off=self.emb_off, **pos))
         i = 0
-        if layers and isinstance(layers[0], LocalAttn):
-            raise UnsupportedLayer(f"{layers[0].name}: local_attention directly on the embedding is not supported (the reference's "
-                                   "stacks put a conv in front of it; the embedding's rows at invalid codons are not zeros)")
-        if layers and isinstance(layers[0], (LengthAttn, AxialAttn)):
-            kind = "transformer_encoder" if isinstance(layers[0], LengthAttn) else "axial_attention"
-            raise UnsupportedLayer(f"{layers[0].name}: {kind} directly on the embedding is not supported (the reference's "
-                                   "stacks put a conv in front of it)")
+        if layers and getattr(layers[0], "on_embedding", None):
+            raise UnsupportedLayer(f"{layers[0].name}: {layers[0].yaml_name} directly on the embedding is not supported "
+                                   f"{layers[0].on_embedding}")
         if not layers or not isinstance(layers[0], Conv):
             # A norm / activation / nmd / residual block - or the pool itself - directly on the Embedding output (the
             # reference's own Embedding -> MaskedBatchNorm -> masked max pool case, tests/unit/test_masked_pooling.py:
@@ -635,229 +424,119 @@ class _Compiler:
             slots.held.discard(s)
             slots.give(s)
 
+    # ---- the layer walk: one handler per layer type, (layers, i, buf, mask, cin) -> (next i, slot, mask slot, channels) --
+    def _conv(self, layers: list, i: int, buf: int, mask: int, cin: int):
+        layer, pending = layers[i], []
+        if not layer.use_masking or mask == L.JG_BUF_NONE:
+            self._refuse_unmasked_reader(f"{layer.name}: a conv without masking")
+        self.dead_margin = None           # a masked conv reads valid positions only: its output holds no dead value
+        om = self._conv_mask(layer, mask)
+        stages = self._base_stages(layer)
+        i, om2 = self._fuse_tail(layers, i + 1, stages, om, layer.filters, pending)
+        out = self.bufs.take()
+        self._emit_conv(layer, buf, mask, stages, om, out)
+        self._flush_nmd(pending, out)
+        self.bufs.give(buf)
+        if mask != om:
+            self.masks.give(mask)
+        return i, out, om2, layer.filters
+
+    def _resblock(self, layers: list, i: int, buf: int, mask: int, cin: int):
+        blk, pending = layers[i], []
+        if not blk.use_masking or mask == L.JG_BUF_NONE:
+            self._refuse_unmasked_reader(f"{blk.name}: a residual block without masking")
+        if self.dead_margin is not None and blk.conv3 is None:
+            # the shortcut adds the block's input as it is (layers.py:1907-1913) while the two convs grow the mask
+            span = (blk.conv1.kernel_size - 1) * blk.conv1.dilation_rate
+            grow = 2 * (span - span // 2)
+            if grow > self.dead_margin:
+                self._refuse_unmasked_reader(f"{blk.name}: a residual block whose output mask grows by {grow} positions "
+                                             f"(its shortcut carries the input's masked positions; room {self.dead_margin})")
+            self.dead_margin -= grow
+        elif blk.conv3 is not None:
+            self.dead_margin = None       # every path into the output is a masked conv
+        in_mask = mask if blk.use_masking else L.JG_BUF_NONE
+        m1 = self._conv_mask(blk.conv1, in_mask)
+        b1 = self.bufs.take()
+        st1 = self._base_stages(blk.conv1) + [self._norm_stage(blk.bn1, m1 != L.JG_BUF_NONE),
+                                              self._stage(L.ST_ACT, arg=act_code(blk.activation))]
+        self._emit_conv(blk.conv1, buf, in_mask, st1, m1, b1)
+        shortcut = buf
+        b3 = None
+        if blk.conv3 is not None:
+            m3 = self._conv_mask(blk.conv3, in_mask)
+            b3 = self.bufs.take()
+            st3 = self._base_stages(blk.conv3) + [self._norm_stage(blk.bn3, m3 != L.JG_BUF_NONE)]
+            self._emit_conv(blk.conv3, buf, in_mask, st3, m3, b3)
+            self.masks.give(m3)
+            shortcut = b3
+        if shortcut == L.JG_BUF_IDS:
+            raise UnsupportedLayer(f"{blk.name}: a residual block cannot be the first layer")
+        m2 = self._conv_mask(blk.conv2, m1)
+        b2 = self.bufs.take()
+        st2 = self._base_stages(blk.conv2)
+        if blk.nmd is not None:             # bn2(return_nmd=True): tap on bn2's input, conv2's mask
+            slot = self.parts.take()
+            st2.append(self._stage(L.ST_NMD, arg=slot))
+            pending.append((blk.nmd, slot, m2))
+        st2 += [self._norm_stage(blk.bn2, m2 != L.JG_BUF_NONE), self._stage(L.ST_ADD, arg=shortcut),
+                self._stage(L.ST_ACT, arg=act_code(blk.activation))]
+        i, m2b = self._fuse_tail(layers, i + 1, st2, m2, blk.conv2.filters, pending)
+        self._emit_conv(blk.conv2, b1, m1, st2, m2, b2)
+        self._flush_nmd(pending, b2)
+        for s in (buf, b1, b3):
+            self.bufs.give(s)
+        for s in (mask, m1):
+            if s != m2:
+                self.masks.give(s)
+        return i, b2, m2b, blk.conv2.filters
+
+    def _eltwise(self, layers: list, i: int, buf: int, mask: int, cin: int):
+        """A norm / activation that no conv in front of it could take: an element-wise op, in place."""
+        layer, pending = layers[i], []
+        if buf == L.JG_BUF_IDS:
+            raise UnsupportedLayer("a norm / activation directly on the embedding is not supported")
+        if buf in self.bufs.held:
+            raise UnsupportedLayer(f"{getattr(layer, 'name', layer.__class__.__name__)}: a norm / activation as the first layer of "
+                                   "a branch is not supported (it runs in place, on the tensor the other branches read)")
+        stages: list = []
+        i, mask2 = self._fuse_tail(layers, i, stages, mask, 0, pending)
+        if pending:
+            raise UnsupportedLayer("an nmd layer must directly follow a conv or residual block")
+        if not stages:
+            raise UnsupportedLayer(f"{getattr(layer, 'name', layer)}: unsupported standalone layer")
+        # a LayerNorm must lead its op (the LayerNorm kernel): cut the list in front of every LN stage
+        cuts = [0] + [j for j, st in enumerate(stages) if st.kind == L.ST_LN and j > 0] + [len(stages)]
+        for a_, b_ in zip(cuts[:-1], cuts[1:]):
+            op = self._op(L.OP_ELTWISE, in_buf=buf, out_buf=buf, out_mask=mask, cout=cin)
+            op.n_stages = b_ - a_
+            for j, st in enumerate(stages[a_:b_]):
+                op.stages[j] = st
+            self.ops.append(op)
+        return i, buf, mask2, cin
+
+    _HANDLERS = {Conv: _conv, ResBlock: _resblock, Norm: _eltwise, Act: _eltwise}
+
     def _walk(self, layers: list, i: int, buf: int, mask: int, cin: int):
         """The layer walk from ``layers[i]`` on: the tensor in slot ``buf`` (``cin`` channels) under mask slot ``mask`` through
         the layers; returns the output slot and the mask slot behind them - or (None, None) behind a ``parallel_branches``,
         which leaves the embedding vector.  The trunk and every branch of a ``parallel_branches`` go through this."""
         while i < len(layers):
             layer = layers[i]
-            pending: list = []
-            if isinstance(layer, Conv):
-                if not layer.use_masking or mask == L.JG_BUF_NONE:
-                    self._refuse_unmasked_reader(f"{layer.name}: a conv without masking")
-                self.dead_margin = None           # a masked conv reads valid positions only: its output holds no dead value
-                om = self._conv_mask(layer, mask)
-                stages = self._base_stages(layer)
-                i, om2 = self._fuse_tail(layers, i + 1, stages, om, layer.filters, pending)
-                out = self.bufs.take()
-                self._emit_conv(layer, buf, mask, stages, om, out)
-                self._flush_nmd(pending, out)
-                self.bufs.give(buf)
-                if mask != om:
-                    self.masks.give(mask)
-                buf, mask = out, om2
-            elif isinstance(layer, ResBlock):
-                blk = layer
-                if not blk.use_masking or mask == L.JG_BUF_NONE:
-                    self._refuse_unmasked_reader(f"{blk.name}: a residual block without masking")
-                if self.dead_margin is not None and blk.conv3 is None:
-                    # the shortcut adds the block's input as it is (layers.py:1907-1913) while the two convs grow the mask
-                    span = (blk.conv1.kernel_size - 1) * blk.conv1.dilation_rate
-                    grow = 2 * (span - span // 2)
-                    if grow > self.dead_margin:
-                        self._refuse_unmasked_reader(f"{blk.name}: a residual block whose output mask grows by {grow} positions "
-                                                     f"(its shortcut carries the input's masked positions; room {self.dead_margin})")
-                    self.dead_margin -= grow
-                elif blk.conv3 is not None:
-                    self.dead_margin = None       # every path into the output is a masked conv
-                in_mask = mask if blk.use_masking else L.JG_BUF_NONE
-                m1 = self._conv_mask(blk.conv1, in_mask)
-                b1 = self.bufs.take()
-                st1 = self._base_stages(blk.conv1) + [self._norm_stage(blk.bn1, m1 != L.JG_BUF_NONE),
-                                                      self._stage(L.ST_ACT, arg=act_code(blk.activation))]
-                self._emit_conv(blk.conv1, buf, in_mask, st1, m1, b1)
-                shortcut = buf
-                b3 = None
-                if blk.conv3 is not None:
-                    m3 = self._conv_mask(blk.conv3, in_mask)
-                    b3 = self.bufs.take()
-                    st3 = self._base_stages(blk.conv3) + [self._norm_stage(blk.bn3, m3 != L.JG_BUF_NONE)]
-                    self._emit_conv(blk.conv3, buf, in_mask, st3, m3, b3)
-                    self.masks.give(m3)
-                    shortcut = b3
-                if shortcut == L.JG_BUF_IDS:
-                    raise UnsupportedLayer(f"{blk.name}: a residual block cannot be the first layer")
-                m2 = self._conv_mask(blk.conv2, m1)
-                b2 = self.bufs.take()
-                st2 = self._base_stages(blk.conv2)
-                if blk.nmd is not None:             # bn2(return_nmd=True): tap on bn2's input, conv2's mask
-                    slot = self.parts.take()
-                    st2.append(self._stage(L.ST_NMD, arg=slot))
-                    pending.append((blk.nmd, slot, m2))
-                st2 += [self._norm_stage(blk.bn2, m2 != L.JG_BUF_NONE), self._stage(L.ST_ADD, arg=shortcut),
-                        self._stage(L.ST_ACT, arg=act_code(blk.activation))]
-                i, m2b = self._fuse_tail(layers, i + 1, st2, m2, blk.conv2.filters, pending)
-                self._emit_conv(blk.conv2, b1, m1, st2, m2, b2)
-                self._flush_nmd(pending, b2)
-                for s in (buf, b1, b3):
-                    self.bufs.give(s)
-                for s in (mask, m1):
-                    if s != m2:
-                        self.masks.give(s)
-                buf, mask = b2, m2b
-            elif isinstance(layer, (Norm, Act)):
-                if buf == L.JG_BUF_IDS:
-                    raise UnsupportedLayer("a norm / activation directly on the embedding is not supported")
-                if buf in self.bufs.held:
-                    raise UnsupportedLayer(f"{getattr(layer, 'name', layer.__class__.__name__)}: a norm / activation as the first layer of "
-                                           "a branch is not supported (it runs in place, on the tensor the other branches read)")
-                stages: list = []
-                i, mask2 = self._fuse_tail(layers, i, stages, mask, 0, pending)
-                if pending:
-                    raise UnsupportedLayer("an nmd layer must directly follow a conv or residual block")
-                if not stages:
-                    raise UnsupportedLayer(f"{getattr(layer, 'name', layer)}: unsupported standalone layer")
-                channels = self._channels_before(layers, i, cin)
-                # a LayerNorm must lead its op (the LayerNorm kernel): cut the list in front of every LN stage
-                cuts = [0] + [j for j, st in enumerate(stages) if st.kind == L.ST_LN and j > 0] + [len(stages)]
-                for a_, b_ in zip(cuts[:-1], cuts[1:]):
-                    op = self._op(L.OP_ELTWISE, in_buf=buf, out_buf=buf, out_mask=mask, cout=channels)
-                    op.n_stages = b_ - a_
-                    for j, st in enumerate(stages[a_:b_]):
-                        op.stages[j] = st
-                    self.ops.append(op)
-                mask = mask2
-            elif isinstance(layer, FrameAttn):
-                if buf == L.JG_BUF_IDS:
-                    raise UnsupportedLayer(f"{layer.name}: cross_frame_attention directly on the embedding is not supported")
-                self._refuse_unmasked_reader(f"{layer.name}: cross_frame_attention (it attends over all six frames of a position)")
-                # CrossFrameAttention does not set supports_masking (layers.py:2283-2384): the norm / activation / pool / conv
-                # behind it see NO mask, and the values the network holds at masked positions flow on as they are
-                i, buf, mask = self._emit_mixer(layers, i, "cross_frame_attention", buf, mask, L.JG_BUF_NONE,
-                                                [lambda src, dst: self._frame_op(layer, src, dst)])
-            elif isinstance(layer, LocalAttn):
-                if buf == L.JG_BUF_IDS:
-                    raise UnsupportedLayer(f"{layer.name}: local_attention directly on the embedding is not supported")
-                # LocalAttention keeps the mask (supports_masking, compute_mask returns it: layers.py:2550, :2627-2628)
-                if mask != L.JG_BUF_NONE:
-                    self.dead_margin = layer.half_window if self.dead_margin is None else min(self.dead_margin, layer.half_window)
-                    self.dead_layer = f"{layer.name} (local_attention)"
-                # one op per block (a tile reads its neighbours' positions as its halo): two slots ping-pong
-                i, buf, mask = self._emit_mixer(layers, i, "local_attention", buf, mask, mask, [
-                    lambda src, dst, j=j: self._op(L.OP_LOCALATTN, in_buf=src, out_buf=dst, in_mask=mask, out_mask=mask, k=layer.heads,
-                                                   cin=layer.channels, cout=layer.channels, arg=layer.ff_dim, stride=layer.half_window,
-                                                   f0=LOCAL_ATTN_EPSILON, w_off=self.blob.add(pack_local_attn(layer, j, self.w)))
-                    for j in range(layer.blocks)])
-            elif isinstance(layer, Hyena):
-                # HyenaBlock multiplies by the mask on entry, behind its layer norm and on exit (layers.py:3109-3132): it
-                # reads valid positions only and writes Keras' exact values everywhere - zeros at masked positions.  So it
-                # may stand behind a local_attention with live dead positions, and its output holds none.  It keeps the mask
-                # (supports_masking, :3072)
-                if mask == L.JG_BUF_NONE:
-                    self._refuse_unmasked_reader(f"{layer.name}: hyena_block without a mask")
-                self.dead_margin = None
-                i, buf, mask = self._emit_mixer(layers, i, "hyena_block", buf, mask, mask, [
-                    lambda src, dst: self._op(L.OP_HYENA, in_buf=src, out_buf=dst, in_mask=mask, out_mask=mask, k=layer.order,
-                                              cin=layer.channels, cout=layer.channels, stride=hyena_table_rows(layer), f0=HYENA_EPSILON,
-                                              arg=(L.HYENA_OUT_PROJ if layer.output_projection else 0) | (L.HYENA_NORMALIZE if layer.filter_normalize else 0),
-                                              w_off=self.blob.add(pack_hyena(layer, self.w)))])
-            elif isinstance(layer, BiLstm):
-                # MaskedBiLSTM hands its mask to the two LSTMs (layers.py:1392-1397): a masked step keeps the states and
-                # repeats the previous output, so x at a masked position reaches no output and every output is defined and
-                # finite - the layer may stand behind a local_attention with live dead positions, and its output holds none.
-                # With ignore_mask (or no mask) it reads every position, and drops the mask (:1405-1410)
-                ignore = layer.ignore_mask or mask == L.JG_BUF_NONE
-                if ignore:
-                    self._refuse_unmasked_reader(f"{layer.name}: masked_bilstm with ignore_mask" if layer.ignore_mask
-                                                 else f"{layer.name}: masked_bilstm without a mask")
-                else:
-                    self.dead_margin = None
-                out_mask = L.JG_BUF_NONE if layer.ignore_mask else mask
-                i, buf, mask = self._emit_mixer(layers, i, "masked_bilstm", buf, mask, out_mask, [
-                    lambda src, dst: self._op(L.OP_BILSTM, in_buf=src, out_buf=dst, in_mask=mask, out_mask=out_mask, k=layer.units,
-                                              cin=layer.cin, cout=layer.channels, arg=L.BILSTM_IGNORE_MASK if layer.ignore_mask else 0,
-                                              w_off=self.blob.add(pack_bilstm(layer, self.w)))])
-            elif isinstance(layer, MultiScaleConv):
-                # Every branch is a MaskedConv1D (layers.py:1217-1280): it multiplies its input by the mask and convolves, so
-                # the layer reads valid positions only and writes defined values everywhere - it may stand behind a
-                # local_attention with live dead positions, and its output holds none (as behind a masked conv).  With
-                # use_masking false in all branches (or no mask) it reads every position, and no mask leaves it
-                masked = layer.use_masking and mask != L.JG_BUF_NONE
-                if masked:
-                    self.dead_margin = None
-                else:
-                    self._refuse_unmasked_reader(f"{layer.name}: multi_scale_conv whose branches do not mask" if mask != L.JG_BUF_NONE
-                                                 else f"{layer.name}: multi_scale_conv without a mask")
-                fields = dict(k=len(layer.branches), cin=layer.cin, cout=layer.channels,
-                              arg=L.MSCONV_ADD if layer.merge == "add" else L.MSCONV_CONCAT,
-                              w_off=self.blob.add(pack_msconv(layer, self.w)))
-                in_mask, out_mask = (mask, self.masks.take()) if masked else (L.JG_BUF_NONE, L.JG_BUF_NONE)
-                if masked:      # the layer's output-mask rule, in front of the op whose output it describes
-                    self.ops.append(self._op(L.OP_MSMASK, in_mask=in_mask, out_mask=out_mask, **fields))
-                i, buf, mask = self._emit_mixer(layers, i, "multi_scale_conv", buf, mask, out_mask, [
-                    lambda src, dst: self._op(L.OP_MSCONV, in_buf=src, out_buf=dst, in_mask=in_mask, out_mask=out_mask, **fields)])
-            elif isinstance(layer, LengthAttn):
-                if buf == L.JG_BUF_IDS:
-                    raise UnsupportedLayer(f"{layer.name}: transformer_encoder directly on the embedding is not supported")
-                self._refuse_unmasked_reader(f"{layer.name}: transformer_encoder (a masked query's output is computed from "
-                                             "its input value, and the layer drops the mask)")
-                # TransformerEncoder sees the implicit mask of its input (Keras 3 fills MultiHeadAttention's query_mask /
-                # value_mask from it) and does not set supports_masking: the norm / activation / pool / conv behind it see NO
-                # mask
-                i, buf, mask = self._emit_mixer(layers, i, "transformer_encoder", buf, mask, L.JG_BUF_NONE,
-                                                [lambda src, dst: self._length_op(layer, src, dst, mask, L.JG_BUF_NONE)])
-            elif isinstance(layer, AxialAttn):
-                if buf == L.JG_BUF_IDS:
-                    raise UnsupportedLayer(f"{layer.name}: axial_attention directly on the embedding is not supported")
-                self._refuse_unmasked_reader(f"{layer.name}: axial_attention (a masked query's output is computed from its "
-                                             "input value, and its frame half attends over all six frames of a position)")
-                # per block (layers.py:2485-2501): r = x; x = length(x) - under the layer's incoming mask in block 0 only:
-                # from block 1 on x is the result of a tensor op inside call() and carries no implicit mask -; x = frame(x),
-                # unmasked; x = norm(x) (masked_layernorm / masked_dyt: with the incoming mask, in every block) + r.  The layer
-                # keeps the mask (supports_masking, :2442); the block-input slot stays taken until the add
-                for j in range(layer.blocks):
-                    la, fa, norm = layer.length(j), layer.frame(j), layer.post_norm(j)
-                    t1 = self.bufs.take()
-                    lm = mask if j == 0 else L.JG_BUF_NONE
-                    self.ops.append(self._length_op(la, buf, t1, lm, lm))
-                    t2 = self.bufs.take()
-                    self.ops.append(self._frame_op(fa, t1, t2))
-                    self.bufs.give(t1)
-                    masked_norm = layer.norm_type in ("masked_layernorm", "masked_dyt") and mask != L.JG_BUF_NONE
-                    stages = [self._norm_stage(norm, masked_norm), self._stage(L.ST_ADD, arg=buf)]
-                    mask2 = mask
-                    if j == layer.blocks - 1:
-                        i, mask2 = self._fuse_tail(layers, i + 1, stages, mask, layer.channels, pending)
-                        if pending:
-                            raise UnsupportedLayer(f"{layer.name}: an nmd tap directly behind axial_attention is not supported "
-                                                   "(the element-wise op that closes the layer carries no partial sums)")
-                    self._emit_ln_tail(layer.name, stages, mask, t2, layer.channels)
-                    self.bufs.give(buf)
-                    buf = t2
-                if mask2 != mask:
-                    self.masks.give(mask)
-                mask = mask2
+            if isinstance(layer, Mixer):
+                (i, buf, mask), cin = layer.emit(self, layers, i, buf, mask), layer.channels
+            elif type(layer) in self._HANDLERS:
+                i, buf, mask, cin = self._HANDLERS[type(layer)](self, layers, i, buf, mask, cin)
             elif isinstance(layer, ParallelBranches):
                 if i + 1 != len(layers):
                     raise UnsupportedLayer(f"{layer.name}: a layer behind a parallel_branches of pooled branches")
-                self._branches(layer, buf, mask, self._channels_before(layers, i, cin))
+                self._branches(layer, buf, mask, cin)
                 return None, None
             elif isinstance(layer, Nmd):
                 raise UnsupportedLayer("an nmd layer must directly follow a conv or residual block")
             else:
                 raise UnsupportedLayer(f"layer {layer!r} is not supported in the representation learner")
         return buf, mask
-
-    def _channels_before(self, layers, i, cin: int) -> int:
-        c = cin
-        for layer in layers[:i]:
-            if isinstance(layer, Conv):
-                c = layer.filters
-            elif isinstance(layer, ResBlock):
-                c = layer.conv2.filters
-            elif isinstance(layer, (BiLstm, MultiScaleConv)):
-                c = layer.channels
-        return c
 
     # ---- heads -----------------------------------------------------------------
     def _head(self, layers: list, in_vec: int, out_vec: int, scratch0: int) -> None:
@@ -955,9 +634,6 @@ class _Compiler:
                                           "concat": L.MERGE_CONCAT}[plan.merge]))
         return Program(self.ops, self.blob.finish(), plan.vocab, plan.n_classes,
                        plan.reliability is not None, plan.nmd_dim, plan.rep_channels, plan.strands)
-
-
-POSITION_ROWS = 8192        # rows of the position table a program carries: windows of up to 24 576 bases (a row = one frame's codons)
 
 
 def sinusoidal_position_rows(n_pos: int, hidden: int, max_wavelength: float) -> np.ndarray:

@@ -17,7 +17,8 @@ from pathlib import Path
 
 import numpy as np
 
-from .plan import AxialAttn, BiLstm, Conv, Dense, FrameAttn, Hyena, LengthAttn, LocalAttn, ModelPlan, MultiScaleConv, Nmd, Norm, ParallelBranches, ResBlock, weight_shapes
+from .mixers import MIXERS, Mixer
+from .plan import Conv, Dense, ModelPlan, Nmd, Norm, ParallelBranches, ResBlock, weight_shapes
 
 
 def random_weights(plan: ModelPlan, seed: int = 38341) -> dict[str, np.ndarray]:
@@ -76,16 +77,13 @@ def attention_layers(plan: ModelPlan) -> list[str]:
     masked_bilstm, multi_scale_conv and parallel_branches layers: the ones with nested sub-layers, whose weights load from
     ``.npz`` only."""
     return [l.name for seq in (plan.rep, plan.classifier, plan.reliability or []) for l in seq
-            if isinstance(l, (FrameAttn, LocalAttn, LengthAttn, AxialAttn, Hyena, BiLstm, MultiScaleConv, ParallelBranches))]
+            if isinstance(l, (Mixer, ParallelBranches))]
 
 
 def attention_kinds(plan: ModelPlan) -> str:
     """The YAML names of the attention / hyena layer kinds the plan holds, for the refusals that name them."""
     layers = [l for seq in (plan.rep, plan.classifier, plan.reliability or []) for l in seq]
-    kinds = [name for cls, name in ((FrameAttn, "cross_frame_attention"), (LocalAttn, "local_attention"),
-                                          (LengthAttn, "transformer_encoder"), (AxialAttn, "axial_attention"),
-                                          (Hyena, "hyena_block"), (BiLstm, "masked_bilstm"),
-                                          (MultiScaleConv, "multi_scale_conv"), (ParallelBranches, "parallel_branches"))
+    kinds = [name for name, cls in (*MIXERS.items(), ("parallel_branches", ParallelBranches))
              if any(isinstance(l, cls) for l in layers)]
     return " / ".join(kinds)
 
@@ -161,7 +159,6 @@ def _natural_key(path: tuple[str, ...]):
     """Keras de-duplicates auto names as ``name``, ``name_1``, ``name_2`` ... and a ResidualBlockStack names its
     blocks ``rep_residual_block_<i>_<j>`` (layers.py:2676-2692): every digit run compares as a number (``_10`` after
     ``_2``), a name without a suffix sorts in front of its ``_1``."""
-    import re
     key = []
     for comp in path:
         toks = [(1, int(t), "") if t.isdigit() else (0, 0, t) for t in re.split(r"(\d+)", comp) if t != ""]
