@@ -315,6 +315,28 @@ static int validate_program(const jg_model *m, const float *weights) {
   return JG_OK;
 }
 
+// The channel widths the conv, element-wise and LayerNorm kernels cover (a lane owns a channel quad; the LayerNorm kernel
+// holds two quads per lane of a wave: 512 channels) - the limits jg_launch_conv, jg_launch_eltwise and jg_launch_layernorm
+// require at every launch, named here so that a model outside them is refused when it is created, not in its first forward.
+// An element-wise op is as wide as its cout (the shape walk holds its input to that).  The conv the table net replaces
+// never reaches jg_launch_conv at rows the table covers and is left to the launch-time check at longer ones.
+static int validate_widths(const jg_model *m) {
+  for (size_t i = 0; i < m->ops.size(); ++i) {
+    const jg_op &op = m->ops[i];
+    if (op.kind == JG_OP_CONV && (int)i != m->tab_conv)
+      JG_REQUIRE(op.cin % 4 == 0 && op.cout % 4 == 0, JG_ERR_UNSUPPORTED,
+                 "op %zu: conv of %d -> %d channels (both must be multiples of 4: a lane of the conv kernels owns a channel quad)", i,
+                 op.cin, op.cout);
+    if (op.kind != JG_OP_ELTWISE) continue;
+    JG_REQUIRE(op.cout % 4 == 0, JG_ERR_UNSUPPORTED,
+               "op %zu: element-wise op of %d channels (a multiple of 4: a lane of the kernel owns a channel quad)", i, op.cout);
+    if (op.n_stages > 0 && op.stages[0].kind == JG_ST_LN)
+      JG_REQUIRE(op.cout <= 512, JG_ERR_UNSUPPORTED,
+                 "op %zu: layer norm over %d channels (up to 512: a lane of the kernel's wave holds two channel quads)", i, op.cout);
+  }
+  return JG_OK;
+}
+
 // The one shape walk: run the program at `l` positions per row and record what every op reads and writes (and check
 // that the shapes line up).  Workspace sizes, FLOPs, tap shapes and the launchers of jg_run.hip all read these records.
 int jg_shape_walk(const jg_model *m, int l, std::vector<OpShape> &shp) {
@@ -573,6 +595,8 @@ extern "C" int jg_model_create(jg_engine *e, const jg_op *ops, int n_ops, const 
   JG_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_overflow), sizeof(int)));
   JG_HIP(hipMemset(m->d_overflow, 0, sizeof(int)));
   rc = jg_prepare_tab(m, weights);
+  if (rc != JG_OK) { jg_model_destroy(m); return rc; }
+  rc = validate_widths(m);                          // (behind jg_prepare_tab: the table net takes the conv it replaces)
   if (rc != JG_OK) { jg_model_destroy(m); return rc; }
   rc = jg_prepare_f16(m, weights);
   if (rc != JG_OK) { jg_model_destroy(m); return rc; }

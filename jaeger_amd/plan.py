@@ -477,7 +477,44 @@ def build_plan(model_cfg: dict) -> ModelPlan:
     elif rel is not None:
         raise ValueError("reliability_model is configured but the representation learner "
                          "produced no NMD tensor")                                # builder.py:636-641
+    _check_kernel_widths(plan)
     return plan
+
+
+#: what the conv, element-wise and LayerNorm kernels (csrc/jg_kernels.hip) cover: a lane owns a channel quad, a lane of the
+#: LayerNorm kernel's wave two of them
+CHANNEL_QUAD = 4
+LAYERNORM_MAX_CHANNELS = 512
+
+
+def _check_kernel_widths(plan: ModelPlan) -> None:
+    """The channel limits of the kernels the representation learner of a translated model runs on (``jg_model_create``
+    refuses the same programs): last, so that every refusal above keeps its wording."""
+    def conv(c: Conv) -> None:
+        if c.cin % CHANNEL_QUAD or c.filters % CHANNEL_QUAD:
+            raise UnsupportedLayer(f"{c.name}: a conv of {c.cin} -> {c.filters} channels (both must be multiples of "
+                                   f"{CHANNEL_QUAD}: a lane of the conv kernels owns a channel quad)")
+
+    def norm(n: Norm) -> None:
+        if n.channels % CHANNEL_QUAD:
+            raise UnsupportedLayer(f"{n.name}: {n.kind} over {n.channels} channels (a multiple of {CHANNEL_QUAD}: a lane of "
+                                   "the element-wise kernels owns a channel quad)")
+        if n.kind == "masked_layernorm" and n.channels > LAYERNORM_MAX_CHANNELS:
+            raise UnsupportedLayer(f"{n.name}: masked_layernorm over {n.channels} channels (up to {LAYERNORM_MAX_CHANNELS}: "
+                                   "a lane of the kernel's wave holds two channel quads)")
+
+    for layer in flat_layers(plan.rep):
+        if isinstance(layer, Conv):
+            conv(layer)
+        elif isinstance(layer, Norm):
+            norm(layer)
+        elif isinstance(layer, ResBlock):
+            for c in (layer.conv1, layer.conv2, layer.conv3):
+                if c is not None:
+                    conv(c)
+            for n in (layer.bn1, layer.bn2, layer.bn3):
+                if n is not None:
+                    norm(n)
 
 
 def _build_strand_plan(model_cfg: dict, sp: dict, graph_input: str, branched: list[bool]) -> ModelPlan:
