@@ -5,7 +5,11 @@ discovery, FASTA validation, output layout ``<output>/<model_id>/<stem>.tsv``, t
 short-contig mode, auxiliary npz writers - with the tf.data pipeline
 (``_build_prediction_dataset`` :186-245) and ``InferModel.predict`` replaced by one window
 table + ``JaegerHipEngine.predict_windows`` call per pass.  Under ``torchrun`` (WORLD_SIZE > 1)
-contigs are sharded over the ranks and gathered on rank 0 (RCCL).
+contigs are sharded over the ranks and gathered on rank 0 (RCCL): ``sharded.py``, imported on that path only.
+
+``run_core`` is a list of stages: :func:`plan_run` (one :class:`RunPlan`), the prediction (``_predict_pipelined``,
+``_predict_sequential`` or ``sharded.predict_sharded``: one :class:`RunResult`), the tables, the side outputs, the summary
+line and the release behind the return.
 """
 
 from __future__ import annotations
@@ -18,6 +22,7 @@ import threading
 import time
 import traceback
 from collections import defaultdict
+from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Any
 
@@ -186,14 +191,6 @@ def predict_records(engine, names: list[str], seqs: list[bytes], fsize: int, str
     """:func:`predict_batch` for records given as Python lists."""
     bases, offsets = frag.concat_records(seqs)
     return predict_batch(engine, frag.FastaBatch(list(names), bases, offsets), fsize, stride, **kw)
-
-
-def _shard_records(lengths: np.ndarray, fsize: int, stride: int | None, world: int):
-    """Whole contigs to ranks, balanced by window count (LPT); returns one index list per rank."""
-    from .dist import lpt_partition
-    step = fsize if stride is None else stride
-    w = np.where(lengths >= fsize, np.maximum(1, (lengths - fsize) // step + 1), 1)
-    return lpt_partition(w, world)
 
 
 class _LazyTableWriter:
@@ -366,12 +363,10 @@ class _Aggregator:
         return merge_data([p[1] for p in parts if p is not None])
 
 
-# ---- torchrun: contig-sharded prediction, one gather of f32 rows ---------------------------------------------
-SHARD_STATS: dict = {}        # filled by the sharded path (tests read it): local / total bases of this rank
+# ---- what outlives a run_core call ------------------------------------------------------------------------
+SHARD_STATS: dict = {}        # filled by the sharded path (sharded.py; tests read it): local / total bases of this rank
 LAST_RUN: dict = {}           # stage split of the last single-GPU run_core of this process (bench.py's e2e leg reads it)
-
-
-_PENDING_RELEASE: list = []      # threads still releasing a finished run's engine / host buffers
+_PENDING_RELEASE: list = []   # threads still releasing a finished run's engine / host buffers
 
 
 def wait_for_release(timeout: float | None = 60.0) -> None:
@@ -381,217 +376,45 @@ def wait_for_release(timeout: float | None = 60.0) -> None:
         _PENDING_RELEASE.pop().join(timeout)
 
 
-def _close_process_group():
-    """Destroy the process group if ``_predict_sharded`` created it (a caller's own group is left alone)."""
-    if SHARD_STATS.pop("own_process_group", False):
-        import torch.distributed as dist
-        if dist.is_initialized():
-            dist.destroy_process_group()
+def _mark(name: str) -> None:
+    """(event, seconds since run_core was entered) onto the run's timeline: where the wall time of a short run goes."""
+    LAST_RUN["timeline"].append((name, round(time.time() - LAST_RUN["t_start_epoch"], 4)))
 
 
-def _coll_device(local_rank: int):
-    import torch
-    import torch.distributed as dist
-    return torch.device("cuda", local_rank) if dist.get_backend() == "nccl" else torch.device("cpu")
+# ---- the run description ------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class RunPlan:
+    """What one ``run_core`` call is to do: decided once by :func:`plan_run`, read by every stage on either path."""
+    options: dict                   # the caller's keywords, for what one stage alone reads (engine options, side outputs)
+    model_name: str
+    model_info: dict
+    model_id: str
+    input_path: Path
+    file_base: str
+    out_dir: Path
+    table_path: Path
+    phage_path: Path
+    fsize: int
+    stride: int | None
+    user_min_len: int | None
+    min_len: int
+    passes: tuple                   # (min_len, max_len, padded) per prediction pass, in the order their rows are reported
+    want: tuple
+    want_full: bool
+    pred_kw: dict                   # pred_to_dict's keywords, but for class_map and term_repeats (known after the run)
+    dust: str                       # "none" | "host" (fragment.dust_mask over the FASTA image) | "device" (in the fused calls)
+    common: dict                    # predict_batch's keywords
+    rank: int
+    world: int
+    local_rank: int
+    sharded: bool
+    piped: bool
+    rc: float
+    pc: int
 
 
-def _bcast(arr: np.ndarray | None, dtype, n: int, dev):
-    """Broadcast a 1-D array from rank 0 (``arr`` is None elsewhere)."""
-    import torch
-    import torch.distributed as dist
-    t = torch.from_numpy(np.ascontiguousarray(arr, dtype)).to(dev) if arr is not None else \
-        torch.zeros(n, dtype=torch.from_numpy(np.zeros(0, dtype)).dtype, device=dev)
-    dist.broadcast(t, src=0)
-    return t.cpu().numpy()
-
-
-def _place_rows(out: np.ndarray, part: np.ndarray, items: np.ndarray, rows_per_item: np.ndarray, first: np.ndarray):
-    """``part`` holds the rows of ``items`` back to back (``rows_per_item[i]`` each); write them to their global
-    positions ``first[i]...`` (vectorised :func:`jaeger_amd.dist.restore_order`)."""
-    n = rows_per_item[items]
-    total = int(n.sum())
-    if total == 0:
-        return
-    local_first = np.cumsum(n) - n
-    dest = np.repeat(first[items] - local_first, n) + np.arange(total, dtype=np.int64)
-    out[dest] = part[:total]
-
-
-def _predict_sharded(make_engine, input_path, fsize, stride, user_min_len, min_len, dust, common, want, lg,
-                     rank, world, local_rank, log_setup):
-    """Rank 0 indexes the FASTA and broadcasts (record byte offsets, lengths); every rank reads, soft-masks, scans
-    and classifies only the contigs LPT deals it; one padded gather of f32 rows (logits | reliability | G C A T counts
-    [| embedding | nmd]) and one of the int32 repeat table go to rank 0, which rebuilds the window metadata from
-    its own window table and restores FASTA order (long pass before short pass)."""
-    import torch
-    import torch.distributed as dist
-
-    from . import dist as jdist
-    from .termini import repeats_frame, terminal_repeat_table
-    if not dist.is_initialized():
-        SHARD_STATS["own_process_group"] = True          # run_core destroys what it created
-        if torch.cuda.is_available():
-            torch.cuda.set_device(local_rank)
-        # RCCL ("nccl") when GPUs are there; JAEGER_DIST_BACKEND=gloo lets several ranks share one GPU (tests)
-        backend = os.environ.get("JAEGER_DIST_BACKEND") or ("nccl" if torch.cuda.is_available() else "gloo")
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if "MASTER_PORT" not in os.environ and world == 1:      # one rank outside torchrun (JAEGER_SHARDED=1)
-            import socket
-            with socket.socket() as sk:
-                sk.bind(("127.0.0.1", 0))
-                os.environ["MASTER_PORT"] = str(sk.getsockname()[1])
-        try:
-            if backend == "nccl":
-                dist.init_process_group(backend, rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
-            else:
-                dist.init_process_group(backend, rank=rank, world_size=world)
-        except Exception as e:              # no fallback to another backend: the error is the result
-            lg.error(f"could not initialise the {backend} process group on rank {rank}/{world} "
-                     f"(HSA_ENABLE_IPC_MODE_LEGACY={os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY')}): {type(e).__name__}: {e}")
-            raise
-    dev = _coll_device(local_rank)
-
-    def all_ok(ok: bool) -> bool:
-        t = torch.tensor([0 if ok else 1], dtype=torch.int32, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        return int(t.item()) == 0
-
-    t_ingest = time.time()
-    ix, head = None, np.zeros(2, np.int64)
-    if rank == 0:
-        try:
-            ix = frag.index_fasta(str(input_path))
-            ok = int((ix.lengths >= min_len).sum())
-            lg.info(f"{ok}/{len(ix)} entries in {input_path}")
-            if ok == 0:
-                raise Exception(f"all records in {input_path} are < {min_len}bp")
-            head[:] = (0, len(ix))
-        except Exception as e:
-            lg.error(e)
-            head[:] = (1, 0)
-    head = _bcast(head if rank == 0 else None, np.int64, 2, dev)
-    if head[0] != 0:
-        sys.exit(1)
-    n_rec = int(head[1])
-    rec_off = _bcast(ix.rec_off if rank == 0 else None, np.int64, n_rec + 1, dev)
-    lengths = _bcast(ix.lengths if rank == 0 else None, np.int64, n_rec, dev)
-    groups = [np.sort(g) for g in _shard_records(lengths, fsize, stride, world)]
-    used = lengths >= min_len                                   # contigs that yield a window in either pass
-    mine = groups[rank][used[groups[rank]]]
-    ok, fa, engine, local, rep_local = True, None, None, None, None
-    t_predict = 0.0
-    two_pass = user_min_len is not None and user_min_len < fsize
-    try:
-        fa = frag.load_fasta_records(str(input_path), rec_off, mine)
-        if not np.array_equal(fa.lengths, lengths[mine]):
-            raise RuntimeError(f"{input_path}: record lengths changed between the index pass and this rank's read")
-        t_ingest = time.time() - t_ingest
-        SHARD_STATS.update(rank=rank, local_bases=int(fa.bases.size), total_bases=int(lengths.sum()),
-                           local_records=len(fa), total_records=n_rec)
-        if dust:
-            t0 = time.time()
-            n_masked = frag.dust_mask(fa)
-            lg.info(f"DUST (window 64, threshold 20): {n_masked} of {fa.bases.size} bases of this rank's "
-                    f"{len(fa)} contigs soft-masked in {time.time() - t0:.2f} s")
-        engine = make_engine()
-        log_setup(engine)
-        t_predict = time.time()
-        kw = dict(common, want=want, meta=False)
-        if two_pass:
-            lg.info(f"Two-pass prediction: long contigs (>= {fsize} bp) then short contigs "
-                    f"({user_min_len}-{fsize - 1} bp)")
-            parts = [predict_batch(engine, fa, fsize, stride, min_len=fsize, max_len=None, **kw),
-                     predict_batch(engine, fa, fsize, stride, min_len=user_min_len, max_len=fsize - 1, padded=True, **kw)]
-        else:
-            parts = [predict_batch(engine, fa, fsize, stride, min_len=min_len, max_len=None, **kw)]
-        cols = [k for k in ("prediction", "reliability", "counts", "embedding", "nmd") if any(k in p for p in parts)]
-        mats = [np.concatenate([np.asarray(p[k], np.float32).reshape(len(p[k]), -1) for k in cols], axis=1)
-                for p in parts if p]
-        widths = {k: next(np.asarray(p[k]).reshape(len(p[k]), -1).shape[1] for p in parts if p) for k in cols}
-        local = np.concatenate(mats, axis=0) if mats else None
-        t_predict = time.time() - t_predict
-        rep_local = terminal_repeat_table(engine.device, fa, fsize)
-    except BaseException as e:               # every rank must reach the collectives below, or the others hang
-        lg.debug(traceback.format_exc())
-        lg.error(f"an error {e} occured during inference on MI355X #{local_rank} (rank {rank})!")
-        ok = False
-    if not all_ok(ok):
-        if engine is not None:
-            engine.close()
-        sys.exit(1)
-    # column layout is the same on every rank (same model); ranks without windows send zero rows
-    wtab = torch.zeros(8, dtype=torch.int64, device=dev)
-    if local is not None:
-        for j, k in enumerate(("prediction", "reliability", "counts", "embedding", "nmd")):
-            wtab[j] = widths.get(k, 0)
-    dist.all_reduce(wtab, op=dist.ReduceOp.MAX)
-    wlist = [int(v) for v in wtab.tolist()[:5]]
-    n_col = sum(wlist)
-    if local is None:
-        local = np.zeros((0, n_col), np.float32)
-    got = jdist.gather_rows(torch.from_numpy(np.ascontiguousarray(local)).to(dev), dst=0)
-    rep = jdist.gather_rows(torch.from_numpy(np.ascontiguousarray(rep_local.reshape(-1, 10))).to(dev), dst=0)
-    class_map = engine.class_map
-    engine.close()
-    if rank != 0:
-        dist.barrier()
-        return None
-    # ---- rank 0: metadata from its own window table, rows back in the reference's emission order -------------
-    passes = [dict(min_len=fsize, max_len=None), dict(min_len=user_min_len, max_len=fsize - 1)] if two_pass else \
-        [dict(min_len=min_len, max_len=None)]
-    tables = [frag.build_window_table(lengths, fsize, stride, common["dynamic_stride"],
-                                      common["dynamic_stride_threshold"], **pk) for pk in passes]
-    per_rec = [np.bincount(t.contig, minlength=n_rec).astype(np.int64) for t in tables]
-    y_pred: dict = {}
-    consumed = [0] * world
-    for t, n_w in zip(tables, per_rec):
-        rows = np.zeros((len(t), n_col), np.float32)
-        first = np.cumsum(n_w) - n_w
-        for q in range(world):
-            items = groups[q][used[groups[q]]]
-            take = int(n_w[items].sum())
-            part = got[q].cpu().numpy()[consumed[q]:consumed[q] + take]
-            _place_rows(rows, part, items, n_w, first)
-            consumed[q] += take
-        out, c0 = {}, 0
-        for k, w in zip(("prediction", "reliability", "counts", "embedding", "nmd"), wlist):
-            if w:
-                out[k] = rows[:, c0:c0 + w]
-            c0 += w
-        counts = np.rint(out.pop("counts")).astype(np.int32)
-        out.update(frag.window_metadata(t, ix.names, counts))
-        y_pred = _concat_predictions(y_pred, out) if len(t) else y_pred
-    res = np.full((n_rec, 10), -1, np.int32)
-    for q in range(world):
-        items = groups[q][used[groups[q]]]
-        res[items] = rep[q].cpu().numpy()
-    term_repeats = repeats_frame(res, ix.names, lengths)
-    lg.info(f"terminal repeats: {int(term_repeats['terminal_repeats'].notna().sum())} of {len(term_repeats)} contigs")
-    dist.barrier()
-    return dict(y_pred=y_pred, term_repeats=term_repeats, class_map=class_map, num=n_rec, t_ingest=t_ingest,
-                t_predict=t_predict)
-
-
-# ---- run_core ---------------------------------------------------------------------------------
-def run_core(**kwargs) -> int:
-    """Equivalent of ``commands/predict.py:run_core``; returns the number of table rows written."""
-    import yaml
-
-    from .engine import JaegerHipEngine
-
-    wait_for_release()
-    t_start = time.time()
-    LAST_RUN.clear()
-    timeline: list = []                     # (event, seconds since run_core was entered): where the wall time of a short run goes
-    LAST_RUN["timeline"] = timeline
-    LAST_RUN["t_start_epoch"] = t_start
-
-    def mark(name):
-        timeline.append((name, round(time.time() - t_start, 4)))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", str(kwargs.get("physicalid", 0))))
-
+def find_model(kwargs: dict) -> tuple[str, dict]:
+    """(name, files) of the model to run: ``--model_path``'s first classification model, or ``--model`` under ``--config``."""
     model_path = kwargs.get("model_path")
     if model_path:
         info = AvailableModels(path=model_path).info
@@ -603,35 +426,35 @@ def run_core(**kwargs) -> int:
             print(f"No classification model found in {model_path}. Expected *_classes.yaml, *_project.yaml "
                   "and *.weights.h5 / *.weights.npz files.", file=sys.stderr)
             sys.exit(1)
-        non_emb = {n: m for n, m in cands.items() if not n.endswith("_embedding")}
-        cands = non_emb or cands
+        cands = {n: m for n, m in cands.items() if not n.endswith("_embedding")} or cands
         model_name = next(iter(cands))
-        model_info = cands[model_name]
-    else:
-        cfg_path = kwargs.get("config")
-        if not cfg_path:
-            print("jaeger_amd: pass --model_path <dir with model/> or --config <json with model_paths>",
-                  file=sys.stderr)
-            sys.exit(1)
-        paths = json.loads(Path(cfg_path).read_text()).get("model_paths", [])
-        info = AvailableModels(path=paths).info
-        model_name = kwargs.get("model")
-        if model_name not in info:
-            print(f"model {model_name!r} not found under {paths}", file=sys.stderr)
-            sys.exit(1)
-        model_info = info[model_name]
-    model_id = get_model_id(model_name)
+        return model_name, cands[model_name]
+    cfg_path = kwargs.get("config")
+    if not cfg_path:
+        print("jaeger_amd: pass --model_path <dir with model/> or --config <json with model_paths>", file=sys.stderr)
+        sys.exit(1)
+    paths = json.loads(Path(cfg_path).read_text()).get("model_paths", [])
+    info = AvailableModels(path=paths).info
+    model_name = kwargs.get("model")
+    if model_name not in info:
+        print(f"model {model_name!r} not found under {paths}", file=sys.stderr)
+        sys.exit(1)
+    return model_name, info[model_name]
 
+
+def plan_run(kwargs: dict) -> RunPlan:
+    """The run description from ``run_core``'s keywords and torchrun's environment."""
+    # (makes the output directory and the run's logger on the way, and refuses - exit 1 - what this path cannot do)
+    model_name, model_info = find_model(kwargs)
+    model_id = get_model_id(model_name)
     input_path = Path(kwargs.get("input"))
     file_base = input_path.stem
     out_dir = Path(kwargs.get("output")) / model_id
     out_dir.mkdir(parents=True, exist_ok=True)
     lg = get_logger(out_dir, Path(f"{file_base}_jaeger.log"), kwargs.get("verbose", 1))
-    fsize, stride = kwargs.get("fsize", 2000), kwargs.get("stride", 1500)
-    user_min_len = kwargs.get("min_len")
+    fsize, user_min_len = kwargs.get("fsize", 2000), kwargs.get("min_len")
     min_len = user_min_len or fsize
-    fa, num, t_ingest = None, 0, 0.0
-    table_path, phage_path = out_dir / f"{file_base}.tsv", out_dir / f"{file_base}_phages.tsv"
+    table_path = out_dir / f"{file_base}.tsv"
     if table_path.exists() and not kwargs.get("overwrite"):
         lg.error("output file exists. enable --overwrite option to overwrite the output file.")
         sys.exit(1)
@@ -648,299 +471,371 @@ def run_core(**kwargs) -> int:
         matrix_path = kwargs.get("crf_transition_matrix")
         if matrix_path:
             crf_kw["crf_transition_matrix"] = json.loads(Path(matrix_path).read_text())
-    precision = "f32" if kwargs.get("exact_f32") else None
-
-    def make_engine():
-        t_eng = time.time()
-        mark("engine_setup_begin")
-        try:
-            return _make_engine()
-        finally:
-            LAST_RUN["engine_create_s"] = round(time.time() - t_eng, 3)
-            mark("engine_ready")
-
-    def _make_engine():
-        # the engine resolves the weights itself (weights.load_weights): the graph's variable bundle - what the reference
-        # executes - first, then the .weights.h5, then the canonical .npz
-        eng = JaegerHipEngine(model_info, device_id=local_rank, chunk=kwargs.get("chunk", 0),
-                              precision=precision, trust_project=True if kwargs.get("trust_project") else None)
-        if kwargs.get("stream_bytes"):              # span budget of the host -> HBM ingest (default 32 MiB)
-            eng.device.set_stream_bytes(int(kwargs["stream_bytes"]))
-        if kwargs.get("dust_stream") is not None:   # A/B: 1 = DUST on the copy stream (default), 0 = on the compute stream
-            from . import _lib as L
-            L.check(eng.device.lib.jg_engine_set_option(eng.device.handle, L.JG_OPT_DUST_ON_COPY_STREAM, int(kwargs["dust_stream"])))
-        return eng
-
-    def ingest():
-        """(under torchrun rank 0 indexes the file and every rank reads its own contigs instead)"""
-        nonlocal fa, num, t_ingest
-        try:
-            t_ingest = time.time()
-            mark("ingest_begin")
-            fa = frag.load_fasta(str(input_path))
-            t_ingest = time.time() - t_ingest
-            mark("ingest_done")
-            num = validate_fasta_entries(fa, min_len=min_len)
-        except Exception as e:
-            lg.error(e)
-            sys.exit(1)
-
-    def engine_failed(e, tb):
-        lg.debug(tb)
-        lg.error(f"could not set up the model on GPU {local_rank}: {e}")
-        sys.exit(1)
-
-    def log_setup(engine):
-        sp = engine.string_processor_config
-        lg.info(f"input file: {input_path.name}")
-        lg.info(f"outpath: {out_dir.resolve()}")
-        lg.info(f"fragment size: {fsize}  stride: {stride}  batch: {kwargs.get('batch', 96)}")
-        lg.info(f"model: {model_id}  arithmetic: {engine.model.precision}  device: MI355X #{local_rank} "
-                f"(rank {rank}/{world})")
-        try:                                   # kernel placement (engines of other kinds have none)
-            pl = engine.model.placement()
-            if pl["small_fused"]:
-                lg.info("kernels: fused small-window kernel (ids -> pooled sums in one launch)")
-            elif engine.model.precision == "f16x3":
-                lg.info(f"kernels: {pl['convs_f16x3']} of {pl['convs']} convolutions on the split-f16 kernels"
-                        + (f", {pl['layout_conversions']} layout conversions" if pl["layout_conversions"] else ""))
-                if pl["convs_f16x3"] < pl["convs"]:
-                    slow = [ln for ln in engine.model.describe().splitlines() if "exact-f32" in ln]
-                    lg.warning("convolutions left on the exact-f32 kernel (about 4x slower):\n  " + "\n  ".join(slow))
-        except AttributeError:
-            pass
-        msg = _crop_length_warning(sp.get("crop_size_codons"), sp.get("crop_size_nt"), fsize)
-        if msg:
-            lg.warning(msg)
-
-    def scan_repeats(device):
-        t_term = time.time()
-        mark("repeat_scan_begin")
-        from .termini import REPORT_MIN_COLUMNS, RepeatColumns, terminal_repeat_table
-        # (alignments of at most 12 columns never reach the table: the scan may skip them - same repeat columns)
-        table = terminal_repeat_table(device, fa, fsize, report_min=REPORT_MIN_COLUMNS)
-        mark("repeat_table_done")
-        rep = RepeatColumns(table, fa.names, fa.lengths)       # (the DataFrame form only where something asks for it)
-        LAST_RUN["terminal_repeats_s"] = round(time.time() - t_term, 3)
-        mark("repeat_scan_done")
-        lg.info(f"terminal repeats: {rep.n_found} of {len(rep)} contigs in {time.time() - t_term:.2f} s")
-        return rep
-
     # DUST soft-masking (on by default like the reference): on the GPU, on the uploaded copy of the bases inside the
     # fused call; --dust-host runs the host scan over the FASTA image instead (same masks bit for bit)
-    dust_any = bool(kwargs.get("dustmask", True))
-    dust = dust_any and bool(kwargs.get("dust_host", False))          # the host pass
-    dust_dev = dust_any and not dust
+    dust = "none" if not kwargs.get("dustmask", True) else "host" if kwargs.get("dust_host", False) else "device"
+    # the long pass, and with --min-len below --fsize the short contigs behind it, one whole-contig window each (padded)
     two_pass = user_min_len is not None and user_min_len < fsize
+    passes = ((fsize, None, False), (user_min_len, fsize - 1, True)) if two_pass else ((min_len, None, False),)
     want = ("prediction", "reliability") + (("embedding",) if kwargs.get("save_embedding") else ()) \
         + (("nmd",) if kwargs.get("save_nmd") else ())
+    want_full = bool(kwargs.get("window_scores") or kwargs.get("prophage"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
     common = dict(dynamic_stride=kwargs.get("dynamic_stride", False),
                   dynamic_stride_threshold=kwargs.get("dynamic_stride_threshold", 10.0),
-                  batch=kwargs.get("batch", 96), pre_cased=dust, want=want, dust_device=dust_dev)
-    term_repeats = None
-    class_map = None
-    t_predict = time.time()
+                  batch=kwargs.get("batch", 96), pre_cased=dust == "host", want=want, dust_device=dust == "device")
     # JAEGER_SHARDED=1: take the sharded path whatever the world size - with ONE rank under torchrun every collective of the
     # 8-GPU run (init over RCCL, broadcasts, the error all_reduce, both padded gathers, barrier) executes on the one GPU
-    sharded = world > 1 or os.environ.get("JAEGER_SHARDED") == "1"
-    if sharded:
-        got = _predict_sharded(make_engine, input_path, fsize, stride, user_min_len, min_len, dust, common, want, lg,
-                               rank, world, local_rank, log_setup)
-        if got is None:                 # ranks other than 0 are done after the gather
-            _close_process_group()
-            return 0
-        y_pred, term_repeats, class_map = got["y_pred"], got["term_repeats"], got["class_map"]
-        num, t_ingest, t_predict = got["num"], got["t_ingest"], got["t_predict"]
-        engine = None
-    else:
-        # ---- one GPU.  A worker thread owns the engine: it sets the model up while the FASTA is read (every core, native),
-        # then runs ONE fused call over all windows of the long pass (DUST on its uploaded spans, encoder, forward; the
-        # library streams the spans through pinned staging and publishes its progress).  Beside it the calling thread scans
-        # for terminal repeats on a stream of its own and aggregates the contigs whose windows are final, so that what is
-        # left behind the forward is the last batch and the TSV.  --no-pipeline runs the same steps one after the other.
-        from concurrent.futures import ThreadPoolExecutor
-        piped = not kwargs.get("no_pipeline")
-        pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="jaeger-gpu") if piped else None
-        t_setup = time.time()
-        f_engine = pool.submit(make_engine) if piped else None
-        ingest()
-        scan: dict = {}
-        th = None
-        if piped:
-            # the terminal-repeat scan starts as soon as the bases are there - a thread and a stream of its own - so that most
-            # of it runs while the model is still being set up: beside the forward its workgroups only get the CUs in the gaps
-            # between the network's launches (the conv and small-window kernels take a CU's whole LDS), and the rows of
-            # finished batches cannot go to the table before the repeat columns exist
+    return RunPlan(options=kwargs, model_name=model_name, model_info=model_info, model_id=model_id, input_path=input_path,
+                   file_base=file_base, out_dir=out_dir, table_path=table_path, phage_path=out_dir / f"{file_base}_phages.tsv",
+                   fsize=fsize, stride=kwargs.get("stride", 1500), user_min_len=user_min_len, min_len=min_len, passes=passes,
+                   want=want, want_full=want_full, pred_kw=dict(fsize=fsize, want_full=want_full, **crf_kw), dust=dust,
+                   common=common, rank=int(os.environ.get("RANK", "0")), world=world,
+                   local_rank=int(os.environ.get("LOCAL_RANK", str(kwargs.get("physicalid", 0)))),
+                   sharded=world > 1 or os.environ.get("JAEGER_SHARDED") == "1", piped=not kwargs.get("no_pipeline"),
+                   rc=kwargs.get("rc", 0.5), pc=kwargs.get("pc", 1))
 
-            def scan_side():
-                try:
-                    from .engine import HipDevice
-                    side = HipDevice(local_rank)
-                    # the scan's short kernels go in front of the network's launches (stream priority): the repeat table is
-                    # there long before the forward ends, and finished batches' rows are written beside it, not behind it
-                    if not kwargs.get("scan_low_priority") and hasattr(side, "set_stream_priority"):   # (duck-typed devices)
-                        side.set_stream_priority(True)
-                    try:
-                        scan["frame"] = scan_repeats(side)
-                    finally:
-                        side.close()
-                except BaseException as e:
-                    scan["error"] = e
 
-            th = threading.Thread(target=scan_side, name="jaeger-termini", daemon=True)
-            th.start()
-        if dust:
-            t_dust = time.time()
-            n_masked = frag.dust_mask(fa)
-            lg.info(f"DUST (window 64, threshold 20): {n_masked} of {fa.bases.size} bases soft-masked in "
-                    f"{time.time() - t_dust:.2f} s")
-        if two_pass:
-            lg.info(f"Two-pass prediction: long contigs (>= {fsize} bp) then short contigs "
-                    f"({user_min_len}-{fsize - 1} bp)")
-        table = frag.build_window_table(fa.lengths, fsize, stride, common["dynamic_stride"],
-                                        common["dynamic_stride_threshold"], fsize if two_pass else min_len, None)
-        n_long = len(table)
-        starts = fa.offsets[table.contig] + table.start
-        mark("window_table_done")
-        LAST_RUN["ingest_and_table_s"] = round(time.time() - t_setup, 3)
+@dataclass
+class RunResult:
+    """What the prediction stage (either path) hands to the tail of ``run_core``."""
+    class_map: dict
+    term_repeats: Any
+    num: int                        # records of the input
+    n_windows: int
+    n_bp: float
+    t_ingest: float
+    t_predict: float
+    engine: Any = None              # (the sharded path has closed its engine behind the gathers)
+    agg: Any = None                 # one GPU: the aggregator and the writer that has the rows flushed so far
+    writer: Any = None
+    y_pred: dict | None = None      # sharded: every window's outputs; one GPU: only for the embedding / NMD files
+    buffers: list = field(default_factory=list)       # the run's large host arrays, released together with the engine
+
+
+def window_totals(seqlens, fsize: int) -> tuple[int, float]:
+    """(windows, bases they cover) of a run, from the per-window record lengths of its passes' window tables."""
+    return sum(len(s) for s in seqlens), sum(float(np.minimum(np.asarray(s, np.int64), fsize).sum()) for s in seqlens)
+
+
+# ---- steps both paths take ----------------------------------------------------------------------------------
+def make_engine(plan: RunPlan):
+    from .engine import JaegerHipEngine
+    opt, t_eng = plan.options, time.time()
+    _mark("engine_setup_begin")
+    try:
+        # the engine resolves the weights itself (weights.load_weights): the graph's variable bundle - what the reference
+        # executes - first, then the .weights.h5, then the canonical .npz
+        eng = JaegerHipEngine(plan.model_info, device_id=plan.local_rank, chunk=opt.get("chunk", 0),
+                              precision="f32" if opt.get("exact_f32") else None,
+                              trust_project=True if opt.get("trust_project") else None)
+        if opt.get("stream_bytes"):                 # span budget of the host -> HBM ingest (default 32 MiB)
+            eng.device.set_stream_bytes(int(opt["stream_bytes"]))
+        return eng
+    finally:
+        LAST_RUN["engine_create_s"] = round(time.time() - t_eng, 3)
+        _mark("engine_ready")
+
+
+def log_setup(plan: RunPlan, engine) -> None:
+    sp = engine.string_processor_config
+    logger.info(f"input file: {plan.input_path.name}")
+    logger.info(f"outpath: {plan.out_dir.resolve()}")
+    logger.info(f"fragment size: {plan.fsize}  stride: {plan.stride}  batch: {plan.common['batch']}")
+    logger.info(f"model: {plan.model_id}  arithmetic: {engine.model.precision}  device: MI355X #{plan.local_rank} "
+                f"(rank {plan.rank}/{plan.world})")
+    try:                                   # kernel placement (engines of other kinds have none)
+        pl = engine.model.placement()
+        if pl["small_fused"]:
+            logger.info("kernels: fused small-window kernel (ids -> pooled sums in one launch)")
+        elif engine.model.precision == "f16x3":
+            logger.info(f"kernels: {pl['convs_f16x3']} of {pl['convs']} convolutions on the split-f16 kernels"
+                        + (f", {pl['layout_conversions']} layout conversions" if pl["layout_conversions"] else ""))
+            if pl["convs_f16x3"] < pl["convs"]:
+                slow = [ln for ln in engine.model.describe().splitlines() if "exact-f32" in ln]
+                logger.warning("convolutions left on the exact-f32 kernel (about 4x slower):\n  " + "\n  ".join(slow))
+    except AttributeError:
+        pass
+    msg = _crop_length_warning(sp.get("crop_size_codons"), sp.get("crop_size_nt"), plan.fsize)
+    if msg:
+        logger.warning(msg)
+
+
+def host_dust(plan: RunPlan, fa: "frag.FastaBatch") -> None:
+    """``--dust-host``: soft-mask the bases this process holds (under torchrun: this rank's contigs) in place."""
+    if plan.dust == "host":
+        t0 = time.time()
+        n_masked = frag.dust_mask(fa)
+        whose = f" of this rank's {len(fa)} contigs" if plan.sharded else ""
+        logger.info(f"DUST (window 64, threshold 20): {n_masked} of {fa.bases.size} bases{whose} soft-masked in "
+                    f"{time.time() - t0:.2f} s")
+
+
+def log_passes(plan: RunPlan) -> None:
+    if len(plan.passes) > 1:
+        logger.info(f"Two-pass prediction: long contigs (>= {plan.fsize} bp) then short contigs "
+                    f"({plan.user_min_len}-{plan.fsize - 1} bp)")
+
+
+# ---- one GPU ------------------------------------------------------------------------------------------------
+# A worker thread owns the engine: it sets the model up while the FASTA is read (every core, native), then runs ONE fused
+# call over all windows of the long pass (DUST on its uploaded spans, encoder, forward; the library streams the spans through
+# pinned staging and publishes its progress).  Beside it the calling thread aggregates the contigs whose windows are final,
+# a third thread scans for terminal repeats on a stream of its own and a fourth writes the rows of finished batches, so that
+# what is left behind the forward is the last batch and the TSV (_predict_pipelined).  --no-pipeline runs the same steps one
+# after the other (_predict_sequential).
+def scan_repeats(plan: RunPlan, device, fa: "frag.FastaBatch"):
+    t_term = time.time()
+    _mark("repeat_scan_begin")
+    from .termini import REPORT_MIN_COLUMNS, RepeatColumns, terminal_repeat_table
+    # (alignments of at most 12 columns never reach the table: the scan may skip them - same repeat columns)
+    table = terminal_repeat_table(device, fa, plan.fsize, report_min=REPORT_MIN_COLUMNS)
+    _mark("repeat_table_done")
+    rep = RepeatColumns(table, fa.names, fa.lengths)       # (the DataFrame form only where something asks for it)
+    LAST_RUN["terminal_repeats_s"] = round(time.time() - t_term, 3)
+    _mark("repeat_scan_done")
+    logger.info(f"terminal repeats: {rep.n_found} of {len(rep)} contigs in {time.time() - t_term:.2f} s")
+    return rep
+
+
+class _SideThread(threading.Thread):
+    """A daemon thread beside the forward: ``result`` or ``error`` of ``fn(*args)`` is for the calling thread to take."""
+
+    def __init__(self, name: str, fn, *args):
+        super().__init__(name=name, daemon=True)
+        self.fn, self.args, self.result, self.error = fn, args, None, None
+
+    def run(self) -> None:
         try:
-            engine = f_engine.result() if piped else make_engine()
-        except Exception as e:
-            engine_failed(e, traceback.format_exc())
-        t_setup = time.time() - t_setup
-        class_map = engine.class_map
-        out = engine.model.host_outputs(n_long, want)
+            self.result = self.fn(*self.args)
+        except BaseException as e:          # noqa: BLE001 - handed to the calling thread
+            self.error = e
 
-        writer = _LazyTableWriter(class_map, table_path, phage_path, kwargs.get("rc", 0.5), kwargs.get("pc", 1))
-        agg = _Aggregator(table, fa.names, out, dict(class_map=class_map, fsize=fsize, term_repeats=None,
-                                                     want_full=bool(kwargs.get("window_scores") or kwargs.get("prophage")),
-                                                     **crf_kw), min_batch=n_long // 16, workers=2 if piped else 1)
 
-        def classify():
+# The terminal-repeat scan of the pipelined run starts as soon as the bases are there - a thread and a stream of its own - so
+# that most of it runs while the model is still being set up: beside the forward its workgroups only get the CUs in the gaps
+# between the network's launches (the conv and small-window kernels take a CU's whole LDS), and the rows of finished batches
+# cannot go to the table before the repeat columns exist.
+def _scan_on_side_device(plan: RunPlan, fa: "frag.FastaBatch"):
+    from .engine import HipDevice
+    side = HipDevice(plan.local_rank)
+    # the scan's short kernels go in front of the network's launches (stream priority): the repeat table is
+    # there long before the forward ends, and finished batches' rows are written beside it, not behind it
+    if hasattr(side, "set_stream_priority"):               # (duck-typed devices)
+        side.set_stream_priority(True)
+    try:
+        return scan_repeats(plan, side, fa)
+    finally:
+        side.close()
+
+
+# Rows of finished batches go to the table beside the forward, on a thread of their own (the calling thread aggregates;
+# formatting a batch's rows is native code and numpy: both run without the interpreter lock).
+def _flush_rows(agg: _Aggregator, writer: _LazyTableWriter, scan: _SideThread, stopping: threading.Event) -> None:
+    while True:
+        last = stopping.is_set()
+        if scan.result is not None:         # (the pass after the stop signal waits for the pool's last batches)
+            agg.flush(writer, scan.result, wait=last)
+        if last:
+            return
+        time.sleep(0.002)
+
+
+class _SingleGpuRun:
+    """The steps the pipelined and the sequential sequence share, and what each leaves for the next."""
+
+    def __init__(self, plan: RunPlan):
+        self.plan = plan
+        self.t_predict = self.t_setup = time.time()
+        self.fa = self.table = self.starts = self.engine = self.out = self.writer = self.agg = None
+        self.num, self.t_ingest, self.y_short = 0, 0.0, {}
+
+    def ingest(self) -> None:
+        """(under torchrun rank 0 indexes the file and every rank reads its own contigs instead)"""
+        try:
             t0 = time.time()
-            mark("fused_call_begin")
-            if n_long:
-                engine.predict_windows(fa.bases, starts, table.length, fsize, pre_cased=dust, want=want,
-                                       dust_records=fa.offsets if dust_dev else None, out=out)
-            mark("fused_call_done")
-            return time.time() - t0
-
-        if piped and th is not None and kwargs.get("scan_first"):
-            th.join()                       # A/B: the repeat scan alone on the GPU, the forward behind it
-        flusher, flush_stop, flush_err = None, None, {}
-        try:
-            f_pred = pool.submit(classify) if piped else None
-            log_setup(engine)
-            if piped:
-                # rows of finished batches go to the table beside the forward, on a thread of their own (the calling thread
-                # aggregates; formatting a batch's rows is native code and numpy: both run without the interpreter lock)
-                flush_stop = threading.Event()
-
-                def flush_side():
-                    try:
-                        while True:
-                            stopping = flush_stop.is_set()
-                            if "frame" in scan:     # (the pass after the stop signal waits for the pool's last batches)
-                                agg.flush(writer, scan["frame"], wait=stopping)
-                            if stopping:
-                                break
-                            time.sleep(0.002)
-                    except BaseException as e:          # noqa: BLE001 - handed to the calling thread
-                        flush_err["error"] = e
-
-                flusher = threading.Thread(target=flush_side, name="jaeger-rows", daemon=True)
-                flusher.start()
-                while not f_pred.done():
-                    agg.names_unique()
-                    agg.advance(engine.device.windows_done())
-                    time.sleep(0.004)
-                t_forward = f_pred.result()
-                agg.advance(n_long, final=True)       # the last contigs: needs no repeat column, runs while the scan finishes
-                mark("aggregated")
-                th.join()
-                flush_stop.set()
-                flusher.join()
-                flusher = None
-                mark("rows_beside_forward_done")
-                if "error" in flush_err:
-                    raise flush_err["error"]
-                if "error" in scan:
-                    raise scan["error"]
-                term_repeats = scan["frame"]
-            else:
-                term_repeats = scan_repeats(engine.device)
-                t_forward = classify()
-            agg.advance(n_long, final=True)
-            if two_pass:
-                y_short = predict_batch(engine, fa, fsize, stride, min_len=user_min_len, max_len=fsize - 1,
-                                        padded=True, **common)
-                agg.add(y_short)
+            _mark("ingest_begin")
+            self.fa = frag.load_fasta(str(self.plan.input_path))
+            self.t_ingest = time.time() - t0
+            _mark("ingest_done")
+            self.num = validate_fasta_entries(self.fa, min_len=self.plan.min_len)
         except Exception as e:
-            writer.abort()                  # rows of finished batches were appended beside the forward: no truncated table stays
-            lg.debug(traceback.format_exc())
-            lg.error(f"an error {e} occured during inference on MI355X #{local_rank}!")
+            logger.error(e)
             sys.exit(1)
-        finally:
-            if flusher is not None:             # (an error path: the row thread must not outlive the writer it uses)
-                flush_stop.set()
-                flusher.join()
-            agg.close()                         # (every batch handed to the pool has been aggregated)
-            if pool is not None:
-                pool.shutdown(wait=True)
-        t_predict = time.time() - t_predict
-        n_windows = n_long + (len(y_short.get("meta_2", ())) if two_pass else 0)
-        n_bp = float(np.minimum(table.seqlen, fsize).sum()) + \
-            (float(np.minimum(np.asarray(y_short["meta_4"], np.int64), fsize).sum()) if two_pass and y_short else 0.0)
-        y_pred = None
-        if kwargs.get("save_embedding") or kwargs.get("save_nmd"):        # the per-window vectors with their headers
-            y_pred = _concat_predictions(agg.slice(0, n_long) if n_long else {}, y_short if two_pass else {})
-        lg.info(f"GPU worker: model set-up {t_setup:.2f} s (beside the FASTA ingest), {n_long} windows classified in "
-                f"{t_forward:.2f} s; {len(agg.parts)} aggregation batches, {agg.busy_s:.2f} s beside the forward")
-        LAST_RUN.update(model_setup_and_ingest_s=round(t_setup, 3), ingest_s=round(t_ingest, 3), forward_s=round(t_forward, 3),
-                        aggregation_batches=len(agg.parts), aggregation_beside_forward_s=round(agg.busy_s, 3),
-                        windows=n_windows, pipelined=bool(piped))
-    if class_map is None:
-        class_map = engine.class_map
-    if dust_dev and engine is not None:
-        lg.info(f"DUST (window 64, threshold 20) on the GPU: {engine.dust_masked_total} bases soft-masked inside the "
-                f"fused calls")
-    t_post = time.time()
 
-    from .postprocess import header_strings, pred_to_dict, write_output
-    if sharded:
-        data, data_full = pred_to_dict(y_pred, class_map=class_map, fsize=fsize, term_repeats=term_repeats,
-                                       want_full=bool(kwargs.get("window_scores") or kwargs.get("prophage")), **crf_kw)
-        n_windows = len(y_pred["meta_2"])
-        n_bp = float(np.minimum(np.asarray(y_pred["meta_4"], np.int64), fsize).sum())
-        LAST_RUN["merge_s"] = round(time.time() - t_post, 3)
-        n_written = write_output(data, labels=class_map.get("class"), indices=class_map.get("index"),
-                                 output_table_path=table_path, output_phage_table_path=phage_path,
-                                 reliability_cutoff=kwargs.get("rc", 0.5), phage_score=kwargs.get("pc", 1))
-    else:
+    def window_table(self) -> None:
+        """Host DUST where asked for, then the long pass's windows."""
+        plan, fa = self.plan, self.fa
+        host_dust(plan, fa)
+        log_passes(plan)
+        self.table = frag.build_window_table(fa.lengths, plan.fsize, plan.stride, plan.common["dynamic_stride"],
+                                             plan.common["dynamic_stride_threshold"], *plan.passes[0][:2])
+        self.starts = fa.offsets[self.table.contig] + self.table.start
+        _mark("window_table_done")
+        LAST_RUN["ingest_and_table_s"] = round(time.time() - self.t_setup, 3)
+
+    def take_engine(self, get_engine) -> None:
+        """``get_engine()`` gives the engine or raises what its set-up raised; then the long pass's rows, aggregator, writer."""
+        plan = self.plan
         try:
-            mark("last_flush_begin")
-            agg.flush(writer, term_repeats)            # what is left: the last batch (and the short-contig pass)
-            n_written = writer.close()
-            mark("tables_closed")
-        except BaseException:
-            writer.abort()
-            raise
-        data_full = agg.result_full()
-        LAST_RUN["merge_s"] = 0.0
-    LAST_RUN["tsv_s"] = round(time.time() - t_post - LAST_RUN["merge_s"], 3)
-    lg.info(f"processed {n_written}/{num} sequences")
-    if kwargs.get("window_scores"):
+            self.engine = get_engine()
+        except Exception as e:
+            logger.debug(traceback.format_exc())
+            logger.error(f"could not set up the model on GPU {plan.local_rank}: {e}")
+            sys.exit(1)
+        self.t_setup = time.time() - self.t_setup
+        n_long, class_map = len(self.table), self.engine.class_map
+        self.out = self.engine.model.host_outputs(n_long, plan.want)
+        self.writer = _LazyTableWriter(class_map, plan.table_path, plan.phage_path, plan.rc, plan.pc)
+        self.agg = _Aggregator(self.table, self.fa.names, self.out, dict(plan.pred_kw, class_map=class_map, term_repeats=None),
+                               min_batch=n_long // 16, workers=2 if plan.piped else 1)
+
+    def classify(self) -> float:
+        """The one fused call over every window of the long pass; its seconds."""
+        plan, fa, t0 = self.plan, self.fa, time.time()
+        _mark("fused_call_begin")
+        if len(self.table):
+            self.engine.predict_windows(fa.bases, self.starts, self.table.length, plan.fsize, pre_cased=plan.dust == "host",
+                                        want=plan.want, dust_records=fa.offsets if plan.dust == "device" else None, out=self.out)
+        _mark("fused_call_done")
+        return time.time() - t0
+
+    def remaining_passes(self) -> None:
+        """The long pass's last contigs, then the passes behind it (the short contigs), each as one more batch."""
+        plan = self.plan
+        self.agg.advance(len(self.table), final=True)
+        for lo, hi, padded in plan.passes[1:]:
+            y = predict_batch(self.engine, self.fa, plan.fsize, plan.stride, min_len=lo, max_len=hi, padded=padded, **plan.common)
+            self.agg.add(y)
+            self.y_short = _concat_predictions(self.y_short, y)
+
+    def inference_failed(self, e: Exception) -> None:
+        """(called while ``e`` is being handled)"""
+        self.writer.abort()             # rows of finished batches were appended beside the forward: no truncated table stays
+        logger.debug(traceback.format_exc())
+        logger.error(f"an error {e} occured during inference on MI355X #{self.plan.local_rank}!")
+        sys.exit(1)
+
+    def result(self, term_repeats, t_forward: float) -> RunResult:
+        plan, agg, n_long = self.plan, self.agg, len(self.table)
+        t_predict = time.time() - self.t_predict
+        n_windows, n_bp = window_totals([self.table.seqlen, self.y_short.get("meta_4", ())], plan.fsize)
+        y_pred = None
+        if plan.options.get("save_embedding") or plan.options.get("save_nmd"):   # the per-window vectors with their headers
+            y_pred = _concat_predictions(agg.slice(0, n_long) if n_long else {}, self.y_short)
+        logger.info(f"GPU worker: model set-up {self.t_setup:.2f} s (beside the FASTA ingest), {n_long} windows classified "
+                    f"in {t_forward:.2f} s; {len(agg.parts)} aggregation batches, {agg.busy_s:.2f} s beside the forward")
+        LAST_RUN.update(model_setup_and_ingest_s=round(self.t_setup, 3), ingest_s=round(self.t_ingest, 3),
+                        forward_s=round(t_forward, 3), aggregation_batches=len(agg.parts),
+                        aggregation_beside_forward_s=round(agg.busy_s, 3), windows=n_windows, pipelined=bool(plan.piped))
+        return RunResult(class_map=self.engine.class_map, term_repeats=term_repeats, num=self.num, n_windows=n_windows,
+                         n_bp=n_bp, t_ingest=self.t_ingest, t_predict=t_predict, engine=self.engine, agg=agg, writer=self.writer,
+                         y_pred=y_pred, buffers=[self.fa, self.table, self.out, agg, self.starts, y_pred])
+
+
+def _predict_sequential(plan: RunPlan) -> RunResult:
+    """``--no-pipeline``: every step on the calling thread, one after the other."""
+    run = _SingleGpuRun(plan)
+    run.ingest()
+    run.window_table()
+    run.take_engine(lambda: make_engine(plan))
+    try:
+        log_setup(plan, run.engine)
+        term_repeats = scan_repeats(plan, run.engine.device, run.fa)
+        t_forward = run.classify()
+        run.remaining_passes()
+    except Exception as e:
+        run.inference_failed(e)
+    finally:
+        run.agg.close()
+    return run.result(term_repeats, t_forward)
+
+
+def _predict_pipelined(plan: RunPlan) -> RunResult:
+    from concurrent.futures import ThreadPoolExecutor
+    pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="jaeger-gpu")
+    run = _SingleGpuRun(plan)
+    f_engine = pool.submit(make_engine, plan)
+    run.ingest()
+    scan = _SideThread("jaeger-termini", _scan_on_side_device, plan, run.fa)
+    scan.start()
+    run.window_table()
+    run.take_engine(f_engine.result)
+    agg, flusher, stop_rows = run.agg, None, threading.Event()
+    try:
+        f_pred = pool.submit(run.classify)
+        log_setup(plan, run.engine)
+        flusher = _SideThread("jaeger-rows", _flush_rows, agg, run.writer, scan, stop_rows)
+        flusher.start()
+        while not f_pred.done():
+            agg.names_unique()
+            agg.advance(run.engine.device.windows_done())
+            time.sleep(0.004)
+        t_forward = f_pred.result()
+        agg.advance(len(run.table), final=True)     # the last contigs: needs no repeat column, runs while the scan finishes
+        _mark("aggregated")
+        scan.join()
+        stop_rows.set()
+        flusher.join()
+        _mark("rows_beside_forward_done")
+        if flusher.error is not None:
+            raise flusher.error
+        if scan.error is not None:
+            raise scan.error
+        run.remaining_passes()
+    except Exception as e:
+        run.inference_failed(e)
+    finally:
+        if flusher is not None:             # (an error path: the row thread must not outlive the writer it uses)
+            stop_rows.set()
+            flusher.join()
+        agg.close()                         # (every batch handed to the pool has been aggregated)
+        pool.shutdown(wait=True)
+    return run.result(scan.result, t_forward)
+
+
+# ---- the tail: tables, side outputs, release ----------------------------------------------------------------
+def _write_tables_single(plan: RunPlan, res: RunResult):
+    """What is left behind the forward: the last batch (and the short-contig pass).  (rows written, per-window data)"""
+    try:
+        _mark("last_flush_begin")
+        res.agg.flush(res.writer, res.term_repeats)
+        n_written = res.writer.close()
+        _mark("tables_closed")
+    except BaseException:
+        res.writer.abort()
+        raise
+    LAST_RUN["merge_s"] = 0.0
+    return n_written, res.agg.result_full()
+
+
+def _write_tables_sharded(plan: RunPlan, res: RunResult):
+    """Rank 0 after the gathers: one aggregation over every window, one table write.  (rows written, per-window data)"""
+    t0 = time.time()
+    from .postprocess import pred_to_dict, write_output
+    data, data_full = pred_to_dict(res.y_pred, class_map=res.class_map, term_repeats=res.term_repeats, **plan.pred_kw)
+    LAST_RUN["merge_s"] = round(time.time() - t0, 3)
+    return write_output(data, labels=res.class_map.get("class"), indices=res.class_map.get("index"),
+                        output_table_path=plan.table_path, output_phage_table_path=plan.phage_path,
+                        reliability_cutoff=plan.rc, phage_score=plan.pc), data_full
+
+
+def _write_side_outputs(plan: RunPlan, res: RunResult, data_full: dict) -> None:
+    """Window scores, prophage segmentation inputs, phage FASTA, embedding / NMD vectors - whichever were asked for."""
+    from .postprocess import header_strings
+    opt, out_dir, file_base = plan.options, plan.out_dir, plan.file_base
+    if opt.get("window_scores"):
         np.savez(out_dir / f"{file_base}_window_scores.npz", headers=header_strings(data_full["headers"]),
                  lengths=data_full["lengths"], predictions=np.array(data_full["predictions"], dtype=object),
                  gc_skews=np.array(data_full["gc_skews"], dtype=object),
                  gcs=np.array(data_full["gcs"], dtype=object))
-    if kwargs.get("prophage"):
+    if opt.get("prophage"):
         # --- prophage segmentation inputs (commands/predict.py:353-442): the per-contig frames logits_to_df_v2 builds
         # from the window logits.  The change-point segmentation, boundary refinement and plots that consume them
         # (ruptures / kneed / pycirclize) are not part of this path; the frames are written for them.
         try:
             from .prophage_inputs import logits_to_df_v2
-            frames = logits_to_df_v2(class_map=class_map, cmdline_kwargs=kwargs, headers=header_strings(data_full["headers"]),
+            frames = logits_to_df_v2(class_map=res.class_map, cmdline_kwargs=opt, headers=header_strings(data_full["headers"]),
                                      predictions=data_full["predictions"], lengths=data_full["lengths"],
                                      gc_skews=data_full["gc_skews"], gcs=data_full["gcs"])
             if frames:
@@ -952,52 +847,81 @@ def run_core(**kwargs) -> int:
                          lengths=np.array([frames[k][2] for k in keys], np.int64),
                          columns=np.array(list(frames[keys[0]][0].columns), dtype=object),
                          tracks=np.array([frames[k][0].to_numpy(np.float64) for k in keys], dtype=object))
-                lg.info(f"prophage segmentation inputs of {len(keys)} contigs (>= {kwargs.get('lc', 500000)} bp) written "
-                        f"to {pro_dir}; the segmentation / plotting step itself is not part of the MI355X path")
+                logger.info(f"prophage segmentation inputs of {len(keys)} contigs (>= {opt.get('lc', 500000)} bp) written "
+                            f"to {pro_dir}; the segmentation / plotting step itself is not part of the MI355X path")
             else:
-                lg.info("no prophage regions found")
+                logger.info("no prophage regions found")
         except Exception as e:
-            lg.error(f"an error {e} occurred during the prophage prediction step")
-            lg.debug(traceback.format_exc())
-    if kwargs.get("getsequences"):
+            logger.error(f"an error {e} occurred during the prophage prediction step")
+            logger.debug(traceback.format_exc())
+    if opt.get("getsequences"):
         # --- phage sequences as FASTA (commands/predict.py:444-456) ---
         from .postprocess import write_fasta_from_results
         out_fasta = out_dir / f"{file_base}_phages_jaeger.fasta"
-        lg.info(f"generating fasta file {out_fasta}")
-        n_seq = write_fasta_from_results(input_path, phage_path, out_fasta)
-        lg.info(f"{n_seq} phage sequences written")
+        logger.info(f"generating fasta file {out_fasta}")
+        n_seq = write_fasta_from_results(plan.input_path, plan.phage_path, out_fasta)
+        logger.info(f"{n_seq} phage sequences written")
+    y_pred = res.y_pred
     if y_pred is not None:
         headers = np.asarray(y_pred.get("meta_0", np.array([], dtype=object))).astype(str)
-        if kwargs.get("save_embedding") and "embedding" in y_pred:
+        if opt.get("save_embedding") and "embedding" in y_pred:
             np.savez(out_dir / f"{file_base}_embedding.npz", embedding=y_pred["embedding"], headers=headers)
-        if kwargs.get("save_nmd") and "nmd" in y_pred:
+        if opt.get("save_nmd") and "nmd" in y_pred:
             np.savez(out_dir / f"{file_base}_nmd.npz", embedding=y_pred["nmd"], headers=headers)   # legacy key name
-    mark("end")
+
+
+def _release_behind(engine, buffers: list) -> None:
+    # the engine's buffers (workspace, pinned staging) are released beside the caller: freeing them takes tens of
+    # milliseconds - a tenth of a short run - and nothing the caller gets depends on it
+    # ... nor on the large host buffers of the run (bases, window table, per-window outputs: unmapping half a gigabyte
+    # takes another 20 ms): ``buffers`` is emptied on that thread too, which drops their last references once the caller
+    # has let go of its own
+    def release():
+        try:
+            engine.close()
+        except Exception as e:          # noqa: BLE001 - nobody joins this thread for its result: say it in the run log
+            logger.warning(f"releasing the engine failed: {type(e).__name__}: {e}")
+        finally:
+            buffers.clear()
+
+    th_close = threading.Thread(target=release, name="jaeger-engine-close")
+    _PENDING_RELEASE.append(th_close)   # the next run_core (and bench.py before it times anything) joins it
+    th_close.start()
+
+
+# ---- run_core ---------------------------------------------------------------------------------
+def run_core(**kwargs) -> int:
+    """Equivalent of ``commands/predict.py:run_core``; returns the number of table rows written."""
+    wait_for_release()
+    t_start = time.time()
+    LAST_RUN.clear()
+    LAST_RUN.update(timeline=[], t_start_epoch=t_start)
+    plan = plan_run(kwargs)
+    if plan.sharded:
+        from . import sharded
+        res = sharded.predict_sharded(plan)
+        if res is None:                 # ranks other than 0 are done after the gather
+            sharded._close_process_group()
+            return 0
+    else:
+        res = (_predict_pipelined if plan.piped else _predict_sequential)(plan)
+    if plan.dust == "device" and res.engine is not None:
+        logger.info(f"DUST (window 64, threshold 20) on the GPU: {res.engine.dust_masked_total} bases soft-masked inside "
+                    f"the fused calls")
+    t_post = time.time()
+    n_written, data_full = (_write_tables_sharded if plan.sharded else _write_tables_single)(plan, res)
+    LAST_RUN["tsv_s"] = round(time.time() - t_post - LAST_RUN["merge_s"], 3)
+    logger.info(f"processed {n_written}/{res.num} sequences")
+    _write_side_outputs(plan, res, data_full)
+    _mark("end")
     t_all = time.time() - t_start
     LAST_RUN.update(behind_forward_s=round(time.time() - t_post, 3), wall_s=round(t_all, 3))
-    lg.info(f"wall time(s) : {t_all:.2f}  ({n_windows} windows; FASTA ingest {t_ingest:.2f} s, "
-            f"encode+forward {t_predict:.2f} s = {n_bp / 1e6 / max(t_predict, 1e-9):.1f} Mbp/s, aggregation+TSV behind the forward "
-            f"{time.time() - t_post:.2f} s; end to end {n_bp / 1e6 / max(t_all, 1e-9):.1f} Mbp/s)")
-    if engine is not None:
-        # the engine's buffers (workspace, pinned staging) are released beside the caller: freeing them takes tens of
-        # milliseconds - a tenth of a short run - and nothing the caller gets depends on it
-        # ... nor on the large host buffers of the run (bases, window table, per-window outputs: unmapping half a gigabyte
-        # takes another 20 ms): their last references are dropped on that thread too
-        garbage = [engine, locals().get("fa"), locals().get("table"), locals().get("out"), locals().get("agg"),
-                   locals().get("starts"), locals().get("y_pred")]
-
-        def release(objs):
-            try:
-                objs[0].close()
-            except Exception as e:          # noqa: BLE001 - nobody joins this thread for its result: say it in the run log
-                lg.warning(f"releasing the engine failed: {type(e).__name__}: {e}")
-            finally:
-                objs.clear()
-
-        th_close = threading.Thread(target=release, args=(garbage,), name="jaeger-engine-close")
-        _PENDING_RELEASE.append(th_close)   # the next run_core (and bench.py before it times anything) joins it
-        th_close.start()
-        del garbage
-    if sharded:
-        _close_process_group()
+    logger.info(f"wall time(s) : {t_all:.2f}  ({res.n_windows} windows; FASTA ingest {res.t_ingest:.2f} s, "
+                f"encode+forward {res.t_predict:.2f} s = {res.n_bp / 1e6 / max(res.t_predict, 1e-9):.1f} Mbp/s, "
+                f"aggregation+TSV behind the forward {time.time() - t_post:.2f} s; "
+                f"end to end {res.n_bp / 1e6 / max(t_all, 1e-9):.1f} Mbp/s)")
+    if res.engine is not None:
+        _release_behind(res.engine, res.buffers)
+    if plan.sharded:
+        sharded._close_process_group()
     return n_written

@@ -286,5 +286,35 @@ def main():
     print("golden vectors written to", HERE)
 
 
+def write_run_core_standin(here):
+    """``run_core`` itself (sequential, one process) with the stand-in engine of tests/run_core_standin.py on its seeded
+    FASTA: both TSVs and the window-scores arrays, as recorded at the commit before ``run_core`` was split into stages
+    (tests/test_run_core_stages.py).  Needs the built library, not the reference:
+
+        python tests/golden/make_golden.py run_core_standin
+    """
+    import tempfile
+    sys.path[:0] = [str(here.parents[1]), str(here.parents[0])]
+    from conftest import make_model_dir
+    from run_core_standin import _run, _write_fasta
+    for tag, min_len in (("none", None), ("600", 600)):
+        with tempfile.TemporaryDirectory() as td:
+            td = Path(td)
+            _write_fasta(td / "in.fasta")
+            make_model_dir(td / "m")
+            _run(td / "out", td / "in.fasta", td / "m", min_len, window_scores=True)
+            got = td / "out" / "38341_1.4M"
+            shutil.copyfile(got / "in.tsv", here / f"run_core_standin_{tag}.tsv")
+            shutil.copyfile(got / "in_phages.tsv", here / f"run_core_standin_{tag}_phages.tsv")
+            ws = np.load(got / "in_window_scores.npz", allow_pickle=True)
+            # (per contig one (windows, classes) block: kept back to back, the split is lengths-independent - `rows`)
+            np.savez(here / f"run_core_standin_{tag}.npz", lengths=np.asarray(ws["lengths"]),
+                     predictions=np.concatenate([np.asarray(p, np.float32) for p in ws["predictions"]], axis=0),
+                     rows=np.array([len(p) for p in ws["predictions"]], np.int64))
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["run_core_standin"]:
+        write_run_core_standin(HERE)
+    else:
+        main()
