@@ -302,9 +302,13 @@ int jg_model_get_precision(const jg_model *m);
 /* How the program was placed: JG_MSTAT_CONVS convolutions, JG_MSTAT_CONVS_F16X3 of them on the split-f16 kernels in
  * mode 1 (the others - 1x1 bypasses, widths or strides outside the kernel - run on the exact-f32 kernel with a layout
  * conversion either side: JG_MSTAT_LAYOUT_CONVERSIONS), JG_MSTAT_SMALL_FUSED = 1 when the whole conv stack runs as the
- * fused small-window kernel.  -1 for an unknown key. */
+ * fused small-window kernel.  -1 for an unknown key.
+ * JG_MSTAT_OPERAND_DIGEST: a 64-bit digest (returned as int64_t) of every operand buffer model creation built and uploaded
+ * for the kernels - the sum mod 2^64 of one FNV-1a hash per buffer, each seeded with its owner; the buffers are read back
+ * from the device and hashed when the key is asked for (tests pin the value). */
 enum { JG_MSTAT_CONVS = 0, JG_MSTAT_CONVS_F16X3 = 1, JG_MSTAT_LAYOUT_CONVERSIONS = 2, JG_MSTAT_SMALL_FUSED = 3,
-       JG_MSTAT_TAP_VARIANT = 4, JG_MSTAT_TAP_INSTANCE = 5, JG_MSTAT_TAP_INSTANCE_OTHER = 6, JG_MSTAT_CONV_INSTANCE0 = 4096 };
+       JG_MSTAT_TAP_VARIANT = 4, JG_MSTAT_TAP_INSTANCE = 5, JG_MSTAT_TAP_INSTANCE_OTHER = 6, JG_MSTAT_OPERAND_DIGEST = 7,
+       JG_MSTAT_CONV_INSTANCE0 = 4096 };
 int64_t jg_model_get_stat(const jg_model *m, int key);
 /* ---- test readback: the tensor one op writes (tests/test_gpu_op_taps.py) ----
  * jg_model_tap_shape: logical shape of what op `op` writes for id rows of l positions, PER WINDOW:

@@ -31,6 +31,7 @@ JG_STAT_STREAM_GROUPS, JG_STAT_STREAM_BYTES, JG_STAT_PEAK_DEVICE_BASES, JG_STAT_
 JG_MSTAT_CONVS, JG_MSTAT_CONVS_F16X3, JG_MSTAT_LAYOUT_CONVERSIONS, JG_MSTAT_SMALL_FUSED = 0, 1, 2, 3
 JG_MSTAT_TAP_VARIANT = 4
 JG_MSTAT_TAP_INSTANCE, JG_MSTAT_TAP_INSTANCE_OTHER, JG_MSTAT_CONV_INSTANCE0 = 5, 6, 4096
+JG_MSTAT_OPERAND_DIGEST = 7
 # JG_MSTAT_TAP_INSTANCE code: the instantiation of the split-f16 conv template a conv's launches ran on (JG_INST_*)
 INST_PART_MASK, INST_K_SHIFT, INST_EP_SHIFT, INST_FLAT, INST_TANH, INST_CW_SHIFT, INST_EP_RT_SHIFT = 0xF, 4, 8, 1 << 24, 1 << 25, 26, 34
 INST_VALID, INST_MIXED = 1 << 60, 1 << 61

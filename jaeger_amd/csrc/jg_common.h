@@ -288,7 +288,8 @@ struct jg_engine {
   unsigned long long *d_dust_cnt = nullptr;
 };
 
-struct ConvHPrep {          // per CONV op: split-f16 operands (built at model creation)
+struct ConvHPrep {          // per op (parallel to jg_model::ops), built at model creation: a CONV op's split-f16 / exact-f32 operands and
+                            // placement decisions; any op's queued layout conversions; the MAXPOOL1D and MSCONV fields marked below
   uint4 *d_wh = nullptr;    // weights [n_half][2][k][cin16/8][128]
   int n_half = 1;           // launches per conv: one per 128 output channels
   int cw = 128;             // workgroup tile width (128, or 64 / 32 for narrow convs)
@@ -349,6 +350,9 @@ struct jg_model {
   float *hy_scratch = nullptr;    // p_0 .. p_order of the hyena ops (jg_hyena.hip), sized by the shape walk
   int64_t hy_cap = 0;             // bytes
   std::string f16_reason;         // why the fast path is unavailable
+  // every operand buffer jg_prepare.hip built and uploaded, with its owner's key: JG_MSTAT_OPERAND_DIGEST hashes them on demand
+  struct Operand { const void *dev; size_t bytes; uint64_t key; };
+  std::vector<Operand> operands;
   int *d_overflow = nullptr;
   float *d_w = nullptr;
   int64_t n_w = 0;

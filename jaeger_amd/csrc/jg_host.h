@@ -115,6 +115,7 @@ int jg_plan_resblocks(jg_model *m, const float *weights);
 int jg_prepare_f32(jg_model *m, const float *weights);
 int jg_prepare_small(jg_model *m, const float *weights);
 void jg_free_small(jg_model *m);
+int64_t jg_operand_digest(const jg_model *m);                   // JG_MSTAT_OPERAND_DIGEST
 const char *jg_tap_refusal(const jg_model *m, size_t i, const PlaceCtx &c, int l, char *why, size_t cap);   // jg_model.hip
 int jg_tap_copy(jg_model *m, size_t i, const OpShape &r, const PlaceCtx &c, int nw, hipStream_t s);
 int jg_effective_chunk(const jg_model *m, int chunk, int l, int64_t n_win);                                  // jg_run.hip

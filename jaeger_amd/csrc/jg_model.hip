@@ -557,6 +557,7 @@ extern "C" int64_t jg_model_get_stat(const jg_model *m, int key) {
     case JG_MSTAT_TAP_VARIANT: return m->tap_variant;
     case JG_MSTAT_TAP_INSTANCE: return jg_conv_inst_get(m, -1, false);
     case JG_MSTAT_TAP_INSTANCE_OTHER: return jg_conv_inst_get(m, -1, true);
+    case JG_MSTAT_OPERAND_DIGEST: return jg_operand_digest(m);
     default:
       if (key >= JG_MSTAT_CONV_INSTANCE0 && key < JG_MSTAT_CONV_INSTANCE0 + (int)m->ops.size())
         return jg_conv_inst_get(m, key - JG_MSTAT_CONV_INSTANCE0, false);

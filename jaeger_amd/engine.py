@@ -283,6 +283,11 @@ class HipModel:
         return {"convs": g(L.JG_MSTAT_CONVS), "convs_f16x3": g(L.JG_MSTAT_CONVS_F16X3),
                 "layout_conversions": g(L.JG_MSTAT_LAYOUT_CONVERSIONS), "small_fused": bool(g(L.JG_MSTAT_SMALL_FUSED))}
 
+    def operand_digest(self) -> int:
+        """64-bit digest of every operand buffer model creation uploaded for the kernels, read back from the device
+        (``JG_MSTAT_OPERAND_DIGEST``)."""
+        return int(self.lib.jg_model_get_stat(self.handle, L.JG_MSTAT_OPERAND_DIGEST)) & 0xFFFFFFFFFFFFFFFF
+
     def describe(self) -> str:
         """Conv by conv: geometry, the kernel it runs on and - for convs left on the exact-f32 kernel - why (``jg_model_describe``)."""
         buf = C.create_string_buffer(1 << 16)
