@@ -560,6 +560,24 @@ int jg_viterbi_decode(const float *logits, int64_t n_windows, int32_t n_classes,
 int jg_terminal_repeats(jg_engine *e, const uint8_t *bases, int64_t n_bases, int bases_loc,
                         const int64_t *offsets, int64_t n_records, int32_t min_len, int32_t *results);
 
+/* ---- batched rectangular local alignment (the att-site search of postprocess/prophages.py:706-873: parasail
+ * sw_trace_scan_16 of the flank left of a prophage region against the flank right of it, direct and
+ * reverse-complemented; scoring and tie rules of jg_terminal_repeats) ---------------------------------------
+ * jobs: n_jobs records on the host, each naming its own spans of `bases`:
+ *   { int64 q_off, r_off; int32 q_len, r_len; int32 flags; int32 pad }   (32 bytes)
+ * query[i] = bases[q_off + i]; ref[j] = bases[r_off + j], or with bit 0 of flags (JG_ALIGN_REVCOMP) the reverse
+ * complement of that span.  q_len and r_len are independent, each 1 .. JG_ALIGN_MAX.
+ * results: (n_jobs, 8) int32 on the host: score, alignment columns, gaps in the query row, gaps in the reference
+ * row, identical columns, end in the query, end in the reference, 0; a job that scores 0 has counts 0 and ends -1.
+ * The alignment starts at (end_q - (columns - query-row gaps) + 1, end_r - (columns - reference-row gaps) + 1).
+ * bases: host or device per bases_loc.  Synchronous; n_jobs == 0 returns at once without touching the device.
+ * JG_ERR_UNSUPPORTED for a length outside 1 .. JG_ALIGN_MAX, JG_ERR_INVALID for a span outside n_bases - both before
+ * any launch. */
+#define JG_ALIGN_MAX 6144
+enum { JG_ALIGN_REVCOMP = 1 };
+int jg_align_pairs(jg_engine *e, const uint8_t *bases, int64_t n_bases, int bases_loc, const void *jobs,
+                   int64_t n_jobs, int32_t *results);
+
 #ifdef __cplusplus
 }
 #endif

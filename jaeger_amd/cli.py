@@ -38,8 +38,10 @@ def main():
 @click.option("--model_path", type=click.Path(exists=True), default=None,
               help="directory containing model/ with *_project.yaml, *_classes.yaml and weights")
 @click.option("--config", type=click.Path(exists=True), default=None)
-@click.option("-p", "--prophage", is_flag=True, help="write the prophage-segmentation input frames of contigs >= --lc "
-                                                     "(the segmentation / plots themselves are not built here)")
+@click.option("-p", "--prophage", is_flag=True, help="find prophages in contigs >= --lc: change-point segmentation of the phage "
+                                                     "track, att-site search at the region boundaries, "
+                                                     "<stem>_prophages/prophages_jaeger.tsv (no gene-based boundary "
+                                                     "refinement, no plots)")
 @click.option("-s", "--sensitivity", type=float, default=1.5)
 @click.option("--lc", type=int, default=500000)
 @click.option("--plot-type", type=click.Choice(["circular", "linear"]), default="circular")

@@ -820,6 +820,53 @@ def _write_tables_sharded(plan: RunPlan, res: RunResult):
                         reliability_cutoff=plan.rc, phage_score=plan.pc), data_full
 
 
+def _prophage_regions_and_report(plan: RunPlan, res: RunResult, data_full: dict, frames: dict, pro_dir: Path) -> None:
+    """``segment`` over the frames, then the att-site search and ``prophages_jaeger.tsv`` (commands/predict.py:378-437).
+    Single and sharded runs alike: the process that holds the frames reads the flanks' contigs from the input file; the
+    device is the run's engine where it is still open, else one opened for the call - and none when no contig has a region."""
+    from .postprocess import header_strings
+    from .prophage_report import prophage_report
+    from .prophage_segment import segment
+    opt = plan.options
+    lc = opt.get("lc", 500_000)
+    phage_cord = segment(frames, cutoff_length=lc, sensitivity=opt.get("sensitivity", 1.5), identifier="phage")
+    if not any(len(cords) > 0 and len(scores) > 0 for cords, scores in phage_cord.values()):
+        logger.info("no prophage regions found")
+        return
+    # contig of a frame -> record of the file: both hold the records of at least lc bases in file order
+    headers, lengths = header_strings(data_full["headers"]), np.asarray(data_full["lengths"])
+    kept = [c for c in range(len(headers)) if lengths[c] >= lc]
+    index = frag.index_fasta(str(plan.input_path))
+    in_file = np.nonzero(np.asarray(index.lengths) >= lc)[0]
+    if len(in_file) != len(kept) or not np.array_equal(np.asarray(index.lengths)[in_file], lengths[kept]):
+        raise ValueError("the contigs of the segmentation frames are not the file's records of at least --lc bases")
+    with_regions = {}                                             # record number -> [ranges, scores]
+    for c, rec in zip(kept, in_file.tolist()):
+        cords, scores = phage_cord.get(f"{headers[c]}", [[], []])
+        if len(cords) > 0 and len(scores) > 0:
+            with_regions[rec] = [cords, scores]
+    recs = sorted(with_regions)
+    fa = frag.load_fasta_records(str(plan.input_path), index.rec_off, recs)      # the bytes as read, before DUST
+    records = [(fa.names[k], fa.sequence(k).decode("latin-1")) for k in range(len(recs))]
+    opened = []
+
+    def align(bases, jobs):
+        from .attscan import align_pairs
+        device = res.engine.device if res.engine is not None else None
+        if device is None:
+            from .engine import HipDevice
+            device = HipDevice(plan.local_rank)
+            opened.append(device)
+        return align_pairs(device, bases, jobs)
+
+    try:
+        prophage_report(fsize=plan.fsize, records=records, prophage_cordinates=[with_regions[r] for r in recs],
+                        outdir=pro_dir, align=align, stride=opt.get("stride"))
+    finally:
+        for device in opened:
+            device.close()
+
+
 def _write_side_outputs(plan: RunPlan, res: RunResult, data_full: dict) -> None:
     """Window scores, prophage segmentation inputs, phage FASTA, embedding / NMD vectors - whichever were asked for."""
     from .postprocess import header_strings
@@ -830,9 +877,10 @@ def _write_side_outputs(plan: RunPlan, res: RunResult, data_full: dict) -> None:
                  gc_skews=np.array(data_full["gc_skews"], dtype=object),
                  gcs=np.array(data_full["gcs"], dtype=object))
     if opt.get("prophage"):
-        # --- prophage segmentation inputs (commands/predict.py:353-442): the per-contig frames logits_to_df_v2 builds
-        # from the window logits.  The change-point segmentation, boundary refinement and plots that consume them
-        # (ruptures / kneed / pycirclize) are not part of this path; the frames are written for them.
+        # --- prophages (commands/predict.py:353-442): the per-contig frames logits_to_df_v2 builds from the window
+        # logits (written out as they always were), the change-point segmentation over them, the att-site search at
+        # the regions' boundaries on the GPU and prophages_jaeger.tsv.  Gene-based boundary refinement and the plots
+        # (pyrodigal-gv / pycirclize) are not part of this path.
         try:
             from .prophage_inputs import logits_to_df_v2
             frames = logits_to_df_v2(class_map=res.class_map, cmdline_kwargs=opt, headers=header_strings(data_full["headers"]),
@@ -848,7 +896,9 @@ def _write_side_outputs(plan: RunPlan, res: RunResult, data_full: dict) -> None:
                          columns=np.array(list(frames[keys[0]][0].columns), dtype=object),
                          tracks=np.array([frames[k][0].to_numpy(np.float64) for k in keys], dtype=object))
                 logger.info(f"prophage segmentation inputs of {len(keys)} contigs (>= {opt.get('lc', 500000)} bp) written "
-                            f"to {pro_dir}; the segmentation / plotting step itself is not part of the MI355X path")
+                            f"to {pro_dir}")
+                logger.info("identifying prophages")
+                _prophage_regions_and_report(plan, res, data_full, frames, pro_dir)
             else:
                 logger.info("no prophage regions found")
         except Exception as e:
