@@ -1,6 +1,7 @@
 // Host side of libjaeger_hip.so, shared by jg_engine / jg_model / jg_prepare / jg_run / jg_predict.hip: the two tables
 // every other piece reads - the shape record of each op at a row length, and where each op runs - and the few functions
-// that cross the files.  No kernel includes this header.
+// that cross the files - and the device-buffer / bucketing helpers of the host halves of jg_termini / jg_alignpairs.hip.  No
+// kernel uses this header.
 #pragma once
 #include <string.h>
 
@@ -139,5 +140,59 @@ static int grow(T **p, int64_t *cap, int64_t need_bytes) {
   JG_HIP(hipMalloc(reinterpret_cast<void **>(p), (size_t)need_bytes));
   *cap = need_bytes;
   return JG_OK;
+}
+// ---- stream-ordered device buffers (jg_termini.hip, jg_alignpairs.hip) -------------------------------------------------
+// Device allocation released with its scope - STREAM-ORDERED (hipMallocAsync / hipFreeAsync on the caller's stream): hipFree
+// waits for every stream of the device, so the repeat scan - which runs beside the network's forward on a stream of its own -
+// used to return only when the forward's whole queue had drained (the repeat table of a million records arrived with the
+// forward's last launch, 0.2 s after the scan's own kernels had ended, and no result row could be written beside the forward).
+struct DevBuf {
+  void *p = nullptr;
+  hipStream_t st = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { if (p) (void)hipFreeAsync(p, st); }
+  int alloc(size_t bytes, hipStream_t s) {
+    st = s;
+    JG_HIP(hipMallocAsync(&p, std::max<size_t>(bytes, 1), s));
+    return JG_OK;
+  }
+  template <typename T>
+  T *as() const { return static_cast<T *>(p); }
+};
+
+template <typename T>
+static int upload(DevBuf &d, const std::vector<T> &v, hipStream_t s) {
+  int rc = d.alloc(v.size() * sizeof(T), s);
+  if (rc != JG_OK) return rc;
+  JG_HIP(hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
+  return JG_OK;
+}
+
+template <typename T>
+static int download(std::vector<T> &v, const DevBuf &d, hipStream_t s) {
+  JG_HIP(hipMemcpyAsync(v.data(), d.p, v.size() * sizeof(T), hipMemcpyDeviceToHost, s));
+  JG_HIP(hipStreamSynchronize(s));
+  return JG_OK;
+}
+
+// Stable bucketing for "one launch per kernel class, tallest class first" (workgroups are dispatched in index order, and a
+// tall job costs many short ones): sorted = the n items whose cls(item) is order[0], then order[1], ..., input order inside a
+// bucket; from[k] = the input index of sorted[k]; bucket b is sorted[first[b] .. first[b + 1]) (first: n_order + 1 entries,
+// or nullptr).  Items of a class that `order` does not name are dropped.
+template <typename T, typename ClassOf>
+static void bucket_by_class(const T *items, size_t n, const int *order, int n_order, ClassOf cls, std::vector<T> &sorted,
+                            std::vector<int64_t> &from, int *first = nullptr) {
+  sorted.clear();
+  from.clear();
+  sorted.reserve(n);
+  from.reserve(n);
+  for (int b = 0; b < n_order; ++b) {
+    if (first) first[b] = (int)sorted.size();
+    for (size_t k = 0; k < n; ++k)
+      if (cls(items[k]) == order[b]) { sorted.push_back(items[k]); from.push_back((int64_t)k); }
+  }
+  if (first) first[n_order] = (int)sorted.size();
 }
 #pragma GCC visibility pop

@@ -15,13 +15,10 @@
 // (real repeats of more than 50 bases) go through termini_kernel.  Same five numbers either way (tests/test_gpu_termini.py
 // runs every case through both).
 //
-// termini_kernel: one workgroup per (contig, DTR|ITR) job.  Thread t owns the query rows [t*R, (t+1)*R) (R <= 16) and walks
-// its strip column by column one step behind thread t-1 (a systolic wavefront): the only values that cross
-// threads are the H / F states of each strip's last row, double-buffered in LDS, one barrier per step.
-// Letters are compared case-insensitively and only A/C/G/T can match (parasail.matrix_create("ACGT", 2, -100)).
-// Ties: H prefers the diagonal, then the gap in the query row (E), then F; E and F prefer extension; the best
-// cell is the first maximum in (column, row) order.  parasail is not installable here: parity with its
-// tie-breaking is unpinned (scores are unique; lengths can differ only between co-optimal alignments).
+// termini_kernel: one workgroup per (contig, DTR|ITR) job, a thin wrapper of the wavefront core of jg_swwave.h (scoring, tie
+// rules and the systolic scheme are described there; align_kernel<R> of jg_alignpairs.hip is the other wrapper): the job is
+// square (n x n), rows per thread R = ceil(n / 256) is a run-time value 1 .. 16, and every state carries two counts
+// (Counts2: columns, gaps in the query row).  LDS is dynamic and sized by the launch's longest scan.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -29,14 +26,13 @@
 #include <algorithm>
 #include <vector>
 
-#include "jg_common.h"
+#include "jg_host.h"
+#include "jg_swwave.h"
 
 namespace {
 
-constexpr int TT = 256;          // threads per job
+constexpr int TT = SW_T;         // threads per job
 constexpr int RMAX = 16;         // rows per thread (scan <= 4096)
-constexpr int NEG = -1000000;    // "minus infinity" that survives a few subtractions
-constexpr int S_MATCH = 2, S_MISMATCH = -100, G_OPEN = 100, G_EXT = 5;
 
 struct TermJob {
   int64_t q_off;   // query  = bases[q_off + i]
@@ -49,111 +45,21 @@ struct TermOut {
   int32_t score, len, fgaps, end_q, end_r;
 };
 
-__device__ __forceinline__ int base_code(uint8_t c) {   // A,C,G,T -> 0..3 (any case), else 4
-  switch (c) {
-    case 'A': case 'a': return 0;
-    case 'C': case 'c': return 1;
-    case 'G': case 'g': return 2;
-    case 'T': case 't': return 3;
-    default: return 4;
-  }
-}
-
 __global__ __launch_bounds__(TT) void termini_kernel(const uint8_t *__restrict__ bases,
                                                      const TermJob *__restrict__ jobs,
                                                      TermOut *__restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const TermJob job = jobs[blockIdx.x];
-  const int n = job.n, tid = threadIdx.x;
-  uint8_t *ref = smem;                                           // n codes
-  int4 *edge = reinterpret_cast<int4 *>(smem + ((n + 15) & ~15)); // [2][TT]: (H, Haux, F, Faux) of a strip's last row
-  int *red = reinterpret_cast<int *>(edge + 2 * TT);              // reduction scratch
-  for (int j = tid; j < n; j += TT) {
-    int c = job.itr ? base_code(bases[job.r_off + n - 1 - j]) : base_code(bases[job.r_off + j]);
-    if (job.itr && c < 4) c = 3 - c;                               // A<->T, C<->G on ACGT = 0..3
-    ref[j] = (uint8_t)c;
-  }
-  const int R = (n + TT - 1) / TT;
-  const int i0 = tid * R;
-  int q[RMAX], hl[RMAX], el[RMAX], hla[RMAX], ela[RMAX];
-#pragma unroll
-  for (int r = 0; r < RMAX; ++r) {
-    const int i = i0 + r;
-    q[r] = (r < R && i < n) ? base_code(bases[job.q_off + i]) : 5;   // 5: row does not exist
-    hl[r] = 0; hla[r] = 0; el[r] = NEG; ela[r] = 0;
-  }
-  edge[tid] = make_int4(0, 0, NEG, 0);
-  edge[TT + tid] = make_int4(0, 0, NEG, 0);
-  int best = 0, best_aux = 0, best_i = -1, best_j = -1;
-  int prev_up_h = 0, prev_up_a = 0;                                  // H[i0-1][j-1]
-  __syncthreads();
-  const int n_active = (n + R - 1) / R;                              // threads that own rows
-  const int steps = n + n_active - 1;
-  for (int step = 0; step < steps; ++step) {
-    const int j = step - tid;
-    int4 pub = make_int4(0, 0, NEG, 0);
-    if (tid < n_active && j >= 0 && j < n) {
-      int up_h = 0, up_a = 0, up_f = NEG, up_fa = 0;
-      if (tid > 0) {
-        const int4 e = edge[((step + 1) & 1) * TT + tid - 1];          // written at step - 1
-        up_h = e.x; up_a = e.y; up_f = e.z; up_fa = e.w;
-      }
-      int dg_h = prev_up_h, dg_a = prev_up_a;
-      prev_up_h = up_h; prev_up_a = up_a;
-      const int rc = ref[j];
-#pragma unroll
-      for (int r = 0; r < RMAX; ++r) {
-        if (r < R && q[r] != 5) {
-          // E: gap in the query row (consumes a ref base): from the left neighbour
-          int e_s, e_a;
-          if (el[r] - G_EXT >= hl[r] - G_OPEN) { e_s = el[r] - G_EXT; e_a = ela[r]; }
-          else { e_s = hl[r] - G_OPEN; e_a = hla[r]; }
-          e_a += (1 << 16) | 1;                                      // one more column, one more query gap
-          // F: gap in the ref row: from above
-          int f_s, f_a;
-          if (up_f - G_EXT >= up_h - G_OPEN) { f_s = up_f - G_EXT; f_a = up_fa; }
-          else { f_s = up_h - G_OPEN; f_a = up_a; }
-          f_a += 1 << 16;
-          const int sub = (q[r] < 4 && q[r] == rc) ? S_MATCH : S_MISMATCH;
-          const int d_s = dg_h + sub, d_a = dg_a + (1 << 16);
-          int h = d_s, ha = d_a;
-          if (e_s > h) { h = e_s; ha = e_a; }
-          if (f_s > h) { h = f_s; ha = f_a; }
-          if (h <= 0) { h = 0; ha = 0; }
-          if (h > best) { best = h; best_aux = ha; best_i = i0 + r; best_j = j; }
-          dg_h = hl[r]; dg_a = hla[r];                               // H[i][j-1] is the next row's diagonal
-          hl[r] = h; hla[r] = ha; el[r] = e_s; ela[r] = e_a;
-          up_h = h; up_a = ha; up_f = f_s; up_fa = f_a;
-        }
-      }
-      pub = make_int4(up_h, up_a, up_f, up_fa);
-    }
-    edge[(step & 1) * TT + tid] = pub;
-    __syncthreads();
-  }
-  // best cell of the job: max score, then smallest column, then smallest row
-  long long key = best > 0 ? (((long long)best << 40) | ((long long)(0xFFFFF - best_j) << 20) | (long long)(0xFFFFF - best_i)) : 0;
-  long long *redl = reinterpret_cast<long long *>(red);
-  int *reda = red + 2 * TT;
-  redl[tid] = key;
-  reda[tid] = best_aux;
-  __syncthreads();
-  for (int s = TT / 2; s > 0; s >>= 1) {
-    if (tid < s && redl[tid + s] > redl[tid]) { redl[tid] = redl[tid + s]; reda[tid] = reda[tid + s]; }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    TermOut o;
-    const long long k = redl[0];
-    o.score = (int)(k >> 40);
-    o.len = reda[0] >> 16;
-    o.fgaps = reda[0] & 0xffff;
-    o.end_r = k ? 0xFFFFF - (int)((k >> 20) & 0xFFFFF) : -1;
-    o.end_q = k ? 0xFFFFF - (int)(k & 0xFFFFF) : -1;
-    out[blockIdx.x] = o;
-  }
+  const int n = job.n;
+  uint8_t *ref = smem;                                            // n codes
+  int4 *edge = reinterpret_cast<int4 *>(smem + ((n + 15) & ~15)); // [2][TT] strip edges
+  long long *redk = reinterpret_cast<long long *>(edge + 2 * TT); // reduction scratch
+  Counts2 *redc = reinterpret_cast<Counts2 *>(redk + TT);
+  sw_load_ref(ref, bases, job.r_off, n, job.itr != 0);
+  const SwBest<Counts2> mine = sw_wavefront<RMAX, Counts2>(bases, job.q_off, n, n, (n + TT - 1) / TT, ref, edge);
+  const SwBest<Counts2> b = sw_reduce_best(mine, redk, redc);
+  if (threadIdx.x == 0) out[blockIdx.x] = TermOut{b.score, b.counts.a >> 16, b.counts.a & 0xffff, b.i, b.j};
 }
-
 
 // ---- fast path: score, end column and row strip of both alignments of a record, one wave per record -----------------
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
@@ -476,42 +382,7 @@ static int launch_fast(const uint8_t *d_bases, const TermRec *d_recs, TermFast *
   return JG_OK;
 }
 
-// ---- the host side's four device stages: upload what the stage reads, launch, bring its results back ------------------
-// Device allocation released with its scope - STREAM-ORDERED (hipMallocAsync / hipFreeAsync on the scan's stream): hipFree
-// waits for every stream of the device, so the scan - which runs beside the network's forward on a stream of its own - used
-// to return only when the forward's whole queue had drained (round 6: the repeat table of a million records arrived with the
-// forward's last launch, 0.2 s after the scan's own kernels had ended, and no result row could be written beside the forward).
-struct DevBuf {
-  void *p = nullptr;
-  hipStream_t st = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { if (p) (void)hipFreeAsync(p, st); }
-  int alloc(size_t bytes, hipStream_t s) {
-    st = s;
-    JG_HIP(hipMallocAsync(&p, std::max<size_t>(bytes, 1), s));
-    return JG_OK;
-  }
-  template <typename T>
-  T *as() const { return static_cast<T *>(p); }
-};
-
-template <typename T>
-static int upload(DevBuf &d, const std::vector<T> &v, hipStream_t s) {
-  int rc = d.alloc(v.size() * sizeof(T), s);
-  if (rc != JG_OK) return rc;
-  JG_HIP(hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
-  return JG_OK;
-}
-
-template <typename T>
-static int download(std::vector<T> &v, const DevBuf &d, hipStream_t s) {
-  JG_HIP(hipMemcpyAsync(v.data(), d.p, v.size() * sizeof(T), hipMemcpyDeviceToHost, s));
-  JG_HIP(hipStreamSynchronize(s));
-  return JG_OK;
-}
-
+// ---- the host side's four device stages: upload what the stage reads, launch, bring its results back (DevBuf: jg_host.h)
 // which alignments of the records have at least k columns at all: bit 0 direct, bit 1 inverted (termini_seed_kernel)
 static int run_seeds(const uint8_t *d_bases, const TermRec *d_recs, int n_recs, int k, std::vector<uint8_t> &flags, hipStream_t s) {
   DevBuf d_flags;
@@ -622,14 +493,11 @@ extern "C" int jg_terminal_repeats(jg_engine *e, const uint8_t *bases, int64_t n
     // index order, and a 4 000-base scan costs a hundred 400-base ones); FASTA order inside a bucket
     const int cls[8] = {64, 48, 32, 24, 16, 12, 8, 7};
     std::vector<TermRec> sr;
-    std::vector<int64_t> so;
-    sr.reserve(recs.size());
-    so.reserve(recs.size());
-    for (int c = 0; c < 8; ++c)
-      for (size_t k = 0; k < recs.size(); ++k)
-        if (fast_rows(recs[k].n) == cls[c]) { sr.push_back(recs[k]); so.push_back(owner[k]); }
+    std::vector<int64_t> from;
+    bucket_by_class(recs.data(), recs.size(), cls, 8, [](const TermRec &r) { return fast_rows(r.n); }, sr, from);
+    for (int64_t &k : from) k = owner[(size_t)k];
     recs.swap(sr);
-    owner.swap(so);
+    owner.swap(from);
   }
   std::vector<uint8_t> ends;
   const bool whole = bases_loc == JG_PTR_HOST && ends_bytes * 10 >= n_bases * 6;

@@ -1,8 +1,14 @@
 """Terminal-repeat scan kernel (jg_terminal_repeats) vs the CPU Smith-Waterman restatement."""
+import functools
+import sys
+from pathlib import Path
+
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
+
+SHORT_SEED = 2        # of _short_cases: a seed at which no case's reference traceback meets a tie
 
 
 def _rand(rng, n):
@@ -80,6 +86,61 @@ def test_kernel_matches_smith_waterman(exact):
     assert d["dtr_exact"] == "DTR" and d["itr_exact"] == "ITR" and d["ltr_dtr"] == "LTR_DTR" and d["big_60kb"] == "LTR_DTR"
     assert d["dtr_mismatch"] == "DTR" and df[df.contig_id == "dtr_mismatch"].repeat_length.iloc[0] == 140
     assert df[df.contig_id == "dtr_gap_in_rear"].repeat_length.iloc[0] == 160
+
+
+@functools.lru_cache(maxsize=None)
+def _short_cases():
+    """name -> (record, expected ten columns), computed once for both runs of the test below."""
+    sys.path.insert(0, str(Path(__file__).resolve().parent))
+    import alignpairs_reference as ref
+    from oracle import termini as ot
+    rng = np.random.Generator(np.random.PCG64(SHORT_SEED))
+    seqs = {f"random_{n}": _rand(rng, n) for n in (1, 2, 13, 64, 255, 256, 257, 399)}
+    for name, n_filler in (("itr_gap_256", 19), ("itr_gap_267", 30)):
+        rep, filler = _rand(rng, 120), _rand(rng, 30)[:n_filler]
+        seqs[name] = rep + filler + ot.reverse_complement(rep[:60] + rep[63:])
+    assert len(seqs["itr_gap_256"]) == 256 and len(seqs["itr_gap_267"]) == 267
+    out = {}
+    for name, seq in seqs.items():
+        row = []
+        for other in (seq, ot.reverse_complement(seq)):       # scan = len: front = rear = the record
+            assert not ref.align(seq, other)["tied"], name      # the seed is chosen so that no traceback meets a tie
+            want = ot.smith_waterman(seq, other)
+            row += [want["score"], want["length"], want["fgaps"], want["end_query"], want["end_ref"]]
+        out[name] = (seq, row)
+    return out
+
+
+@pytest.mark.parametrize("exact", [0, 1])
+def test_short_records_through_the_exact_kernel(exact):
+    """Records shorter than the 400-base scan (min_len = 1: scan = the whole record): 1, 2, 13, 64, 255, 256, 257 and 399
+    random bases - termini_kernel at one row per thread with fewer active threads than a workgroup, exactly a workgroup,
+    and two rows per thread - and two records whose inverted repeat misses 3 bases in one copy, 256 and 267 bases long:
+    their ITR alignment carries a gap across strip boundaries at 1 and at 2 rows per thread.  All ten columns equal the CPU
+    Smith-Waterman, through the exact kernel alone and through the packed pass in front of it; a plain record's DTR is the
+    record on itself: (2 n, n, 0, n - 1, n - 1)."""
+    from jaeger_amd import fragment as frag
+    from jaeger_amd import _lib as L
+    from jaeger_amd.engine import HipDevice
+    import ctypes as C
+    cases = _short_cases()
+    names = list(cases)
+    bases, offsets = frag.concat_records([cases[k][0].encode() for k in names])
+    dev = HipDevice(0)
+    L.check(dev.lib.jg_engine_set_option(dev.handle, L.JG_OPT_TERMINI_EXACT, exact))
+    res = np.full((len(names), 10), -7, np.int32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    L.check(dev.lib.jg_terminal_repeats(dev.handle, ptr(bases), bases.size, L.JG_PTR_HOST, ptr(offsets), len(names), 1, ptr(res)))
+    dev.close()
+    for k, name in enumerate(names):
+        seq, want = cases[name]
+        assert res[k].tolist() == want, (name, res[k].tolist(), want)
+        if name.startswith("random_"):
+            n = len(seq)
+            assert want[:5] == [2 * n, n, 0, n - 1, n - 1], name
+    for name in ("itr_gap_256", "itr_gap_267"):                # the ITR side reports the planted repeat with its 3-base gap
+        score, length, fgaps, end_q, end_r = cases[name][1][5:]  # in the reference row (a chance match may extend it)
+        assert score >= 2 * 117 - 110 and fgaps == 0 and length == end_q + 1 >= 120 and end_r == end_q - 3, cases[name][1]
 
 
 def test_short_records_are_skipped():
