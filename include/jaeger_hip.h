@@ -262,10 +262,27 @@ int jg_engine_sync(jg_engine *e);
  * JG_OPT_STREAM_PRIORITY (default 0; round 6): 1 = the engine's stream is re-created at the device's HIGHEST stream priority (0: the
  *   default one again); set it on an idle engine, before its first launch.  run_core gives it to the side engine of the
  *   terminal-repeat scan: its short kernels then take the CUs the network's launches free between each other instead of
- *   queueing behind them, the repeat table exists long before the forward ends, and finished batches' rows are written beside it. */
+ *   queueing behind them, the repeat table exists long before the forward ends, and finished batches' rows are written beside it.
+ * JG_OPT_POISON_WORKSPACE (default -1 = off; 0 .. 255 = a byte pattern, anything else JG_ERR_INVALID): a debug option for the
+ *   tests that prove a forward independent of what earlier calls left in the model's grow-only workspace.  While it is on, every
+ *   launch group of jg_forward and jg_predict_windows (each chunk, each pass of a streamed group, and the second attempt of the
+ *   range-guard fallback) first fills, with that byte and over its whole ALLOCATED capacity, every scratch buffer a kernel may read
+ *   before a kernel of the same group wrote it: the activation slots act[], the mask slots msk[], the NMD partial rows nmd_part[],
+ *   the vector slots vec[], the layout-conversion scratch cvt_scratch, the hyena projection scratch hy_scratch, the fused max
+ *   pool's partial rows pool_part, the strand merge rows merged[], the small-window net's partial rows (d_part) and the tap's
+ *   conversion target tap_buf.  pool_part, merged[] and d_part may be (re)allocated by a launcher inside the group: they are
+ *   then filled where they grew (tap_buf grows inside the group too, and is rewritten whole before it is read).  The fill is a hipMemsetAsync on the group's own stream, so it runs behind every copy of the previous
+ *   group's outputs (those copies - to the caller's arrays or to the pinned staging of the streamed path - are queued on the
+ *   same stream) and needs no event.  Not filled: buffers that hold inputs, indices or offsets (the id tensor, the window
+ *   table, the counts, the uploaded bases and their device spans, the record table, the encoder's lookup table), the operand
+ *   buffers built at model creation, and the range-guard flag - a stale index would be an access out of bounds, not a wrong
+ *   number.  No region is skipped for having been written once at allocation (vec[] is cleared there, and filled here all the
+ *   same).  Off, the forward is as before: no launch and no synchronisation is added.  0xFF reads as NaN in f32 and f16 and
+ *   as a valid mask byte, 0x7B as 1.3e36 / 61280 (finite, so it wins a maximum a NaN may lose) and a valid mask byte, 0x00 is
+ *   what a fresh process sees (tests/test_gpu_poison.py). */
 enum { JG_OPT_STREAM_BYTES = 1, JG_OPT_CONV_PC = 2, JG_OPT_TERMINI_EXACT = 3, JG_OPT_DUST_ON_COPY_STREAM = 4,
        JG_OPT_TABLE_NET_LDS = 5, JG_OPT_RESET_PROGRESS = 6, JG_OPT_FUSE_RESBLOCK = 7, JG_OPT_TERMINI_REPORT_MIN = 8,
-       JG_OPT_STREAM_PRIORITY = 9 };
+       JG_OPT_STREAM_PRIORITY = 9, JG_OPT_POISON_WORKSPACE = 10 };
 int jg_engine_set_option(jg_engine *e, int key, int64_t value);
 /* statistics of the engine's last jg_predict_windows call: number of streamed groups (0 = not streamed), bytes sent
  * through the staging buffers, peak bytes of bases resident on the device.  JG_STAT_WINDOWS_DONE may be read from

@@ -266,6 +266,7 @@ struct jg_engine {
   int tab_lds_only = 0;           // JG_OPT_TABLE_NET_LDS: keep the table net on the LDS-table kernel
   int fuse_resblock = 1;          // JG_OPT_FUSE_RESBLOCK: narrow residual blocks as one launch (jg_resblock.hip)
   int conv_pc = 0;                // JG_OPT_CONV_PC: producer / consumer kernel for the 128-channel five-tap convs
+  int poison = -1;                // JG_OPT_POISON_WORKSPACE: byte every launch group fills the models' scratch buffers with (-1: off)
   // streamed ingest of host-resident bases (jg_predict_windows): spans above `stream_bytes` go through two pinned
   // staging buffers and two device buffers on a copy stream, record group by record group
   int64_t stream_bytes = (int64_t)32 << 20;

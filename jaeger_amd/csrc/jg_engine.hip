@@ -114,6 +114,11 @@ extern "C" int jg_engine_set_option(jg_engine *e, int key, int64_t value) {
     case JG_OPT_FUSE_RESBLOCK:
       e->fuse_resblock = value != 0;
       return JG_OK;
+    case JG_OPT_POISON_WORKSPACE:
+      JG_REQUIRE(value >= -1 && value <= 255, JG_ERR_INVALID, "jg_engine_set_option: JG_OPT_POISON_WORKSPACE takes -1 (off) or a byte 0 .. 255, got %lld",
+                 (long long)value);
+      e->poison = (int)value;
+      return JG_OK;
     case JG_OPT_RESET_PROGRESS:
       e->windows_done.store(0, std::memory_order_release);
       return JG_OK;

@@ -322,6 +322,8 @@ static int predict_streamed(jg_model *m, const uint8_t *bases, int64_t n_bases, 
     for (int k = 0; k < 4; ++k)
       dst[k] = user[k] == nullptr ? nullptr
                                   : (host_out ? reinterpret_cast<float *>(io_b + off_out[k]) : user[k] + g.w0 * width[k]);
+    // (JG_OPT_POISON_WORKSPACE: every pass fills the workspace on `s` first - behind the previous group's copies into its
+    // pinned staging, which are queued on `s` as well; grp_done guards the staging, not the workspace)
     erc = jg_forward_chunks(m, shp, m->d_ids, nw, l_pad, dst[0], dst[1], dst[2], dst[3], out_loc, fchunk, s);
     if (erc != JG_OK) return erc;
     if (counts != nullptr && host_out)

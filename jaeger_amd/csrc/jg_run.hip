@@ -85,6 +85,32 @@ static double conv_flops(const jg_op &op, const OpShape &r, int nw) {
   return 2.0 * op.k * op.cin * op.cout * (double)nw * r.in.frames * r.L_out;
 }
 
+// ---- JG_OPT_POISON_WORKSPACE (include/jaeger_hip.h lists the buffers and what is left alone) -------------------------
+static int poison_fill(const jg_engine *e, void *p, int64_t bytes, hipStream_t s) {
+  if (e->poison >= 0 && p != nullptr && bytes > 0) JG_HIP(hipMemsetAsync(p, e->poison, (size_t)bytes, s));
+  return JG_OK;
+}
+
+// in front of a launch group's first launch, behind jg_ensure_workspace: every scratch buffer over its allocated capacity.
+// Stream order puts the fill behind the previous group's output copies (copy_out queues them on the same stream).
+static int poison_workspace(jg_model *m, hipStream_t s) {
+  const jg_engine *e = m->e;
+  if (e->poison < 0) return JG_OK;
+  const int64_t f = (int64_t)sizeof(float);
+  int rc = JG_OK;
+  for (int i = 0; i < JG_MAX_BUFS && rc == JG_OK; ++i)
+    if ((rc = poison_fill(e, m->act[i], m->act_cap[i] * f, s)) == JG_OK && (rc = poison_fill(e, m->msk[i], m->msk_cap[i], s)) == JG_OK)
+      rc = poison_fill(e, m->nmd_part[i], m->nmd_cap[i] * f, s);
+  for (int i = 0; i < JG_MAX_VECS && rc == JG_OK; ++i)
+    if ((rc = poison_fill(e, m->vec[i], m->vec_cap[i] * f, s)) == JG_OK) rc = poison_fill(e, m->merged[i], m->merged_cap[i], s);
+  if (rc == JG_OK) rc = poison_fill(e, m->cvt_scratch, m->cvt_cap * f, s);
+  if (rc == JG_OK) rc = poison_fill(e, m->hy_scratch, m->hy_cap, s);
+  if (rc == JG_OK) rc = poison_fill(e, m->pool_part, m->pool_part_cap * f, s);
+  if (rc == JG_OK) rc = poison_fill(e, m->tap_buf, m->tap_cap, s);
+  if (rc == JG_OK && m->small != nullptr) rc = poison_fill(e, m->small->d_part, m->small->part_cap, s);
+  return rc;
+}
+
 // ---- launchers: (model, op index, the op's shape record, [ids], rows of the chunk, stream) ---------------------------
 static void resolve_stages(const jg_model *m, const jg_op &op, StageArg *dst, int *n) {
   *n = op.n_stages;
@@ -107,8 +133,9 @@ static int launch_small_net(jg_model *m, const OpShape &c0, const uint8_t *d_ids
   jg_engine *e = m->e;
   JgSmallNet *sn = m->small;
   const int64_t rows = (int64_t)nw * 6;
+  const int64_t had = sn->part_cap;
   int rc = grow(&sn->d_part, &sn->part_cap, rows * sn->n_slots * JG_SMALL_PARTW * (int64_t)sizeof(float));
-  if (rc != JG_OK) return rc;
+  if (rc != JG_OK || (sn->part_cap != had && (rc = poison_fill(e, sn->d_part, sn->part_cap, s)) != JG_OK)) return rc;
   static const int dbg = [] { const char *ev = jg_exp_env("JG_SMALL_DBG"); return ev ? atoi(ev) : 0; }();
   JgSmallArgs a;
   memset(&a, 0, sizeof(a));
@@ -382,6 +409,8 @@ static int launch_conv_f16(jg_model *m, size_t i, const OpShape &r, const uint8_
       m->pool_part = nullptr;
       JG_HIP(hipMalloc(reinterpret_cast<void **>(&m->pool_part), (size_t)need * sizeof(float)));
       m->pool_part_cap = need;
+      const int prc = poison_fill(e, m->pool_part, need * (int64_t)sizeof(float), s);
+      if (prc != JG_OK) return prc;
     }
     a.pool_out = m->pool_part;
   }
@@ -649,8 +678,9 @@ static int copy_out(jg_model *m, int slot, int width, float *dst, int64_t row0, 
   if (m->strands > 1) {
     // branched model: the vector slot holds one row per strand; the window's row is their merge (the prediction by the
     // classifier's merge layer, every other output by Average - builder.py:776-791)
-    const int rc = grow(&m->merged[slot], &m->merged_cap[slot], (int64_t)nw * width * (int64_t)sizeof(float));
-    if (rc != JG_OK) return rc;
+    const int64_t had = m->merged_cap[slot];
+    int rc = grow(&m->merged[slot], &m->merged_cap[slot], (int64_t)nw * width * (int64_t)sizeof(float));
+    if (rc != JG_OK || (m->merged_cap[slot] != had && (rc = poison_fill(m->e, m->merged[slot], m->merged_cap[slot], s)) != JG_OK)) return rc;
     const int kind = slot == 2 ? m->merge_kind : JG_MERGE_AVERAGE;
     // (`width` is the OUTPUT's: a concatenated prediction is `strands` head vectors wide)
     const int mrc = jg_launch_strand_merge(src, (int)src_ld, nw, m->strands, kind == JG_MERGE_CONCAT ? width / m->strands : width, kind,
@@ -686,7 +716,9 @@ int jg_forward_chunks(jg_model *m, const std::vector<OpShape> &shp, const uint8_
   for (int64_t w0 = 0; w0 < n_win; w0 += chunk) {
     const int nw = (int)std::min<int64_t>(chunk, n_win - w0);
     m->tap_row0 = w0 * m->strands;
-    int rc = run_chunk(m, shp, d_ids + w0 * m->strands * m->id_frames * (int64_t)l * m->id_bytes, nw * m->strands, l, s);
+    int rc = poison_workspace(m, s);
+    if (rc != JG_OK) return rc;
+    rc = run_chunk(m, shp, d_ids + w0 * m->strands * m->id_frames * (int64_t)l * m->id_bytes, nw * m->strands, l, s);
     if (rc != JG_OK) return rc;
     if ((rc = copy_out(m, 2, w_pred, prediction, w0, nw, out_loc, s)) != JG_OK) return rc;
     if ((rc = copy_out(m, 3, w_rel, reliability, w0, nw, out_loc, s)) != JG_OK) return rc;

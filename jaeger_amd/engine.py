@@ -121,6 +121,12 @@ class HipDevice:
         (JG_OPT_FUSE_RESBLOCK; A/B timing and tests)."""
         L.check(self.lib.jg_engine_set_option(self.handle, L.JG_OPT_FUSE_RESBLOCK, int(bool(on))), "jg_engine_set_option")
 
+    def set_poison(self, byte: int | None) -> None:
+        """Debug: every launch group of a forward first fills the model's scratch buffers with ``byte`` (0 .. 255), over their
+        allocated capacity; ``None`` turns it off again (JG_OPT_POISON_WORKSPACE; tests/test_gpu_poison.py)."""
+        L.check(self.lib.jg_engine_set_option(self.handle, L.JG_OPT_POISON_WORKSPACE, -1 if byte is None else int(byte)),
+                "jg_engine_set_option")
+
     def reset_progress(self):
         """``windows_done()`` back to 0 (JG_OPT_RESET_PROGRESS): called before a ``predict_windows`` call is handed to another
         thread, so that a poller which starts first never reads the previous call's final count."""
