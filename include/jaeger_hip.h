@@ -595,6 +595,21 @@ enum { JG_ALIGN_REVCOMP = 1 };
 int jg_align_pairs(jg_engine *e, const uint8_t *bases, int64_t n_bases, int bases_loc, const void *jobs,
                    int64_t n_jobs, int32_t *results);
 
+/* ---- the same alignment for flanks longer than JG_ALIGN_MAX ---------------------------------------------------------
+ * A flank of prophage_report (postprocess/prophages.py:773-780) is scan_length + off_set bases: scan_length =
+ * min(max(int(0.04 len), 400), 4000) outside the region (:773) and off_set inside it, off_set = region_len // 4 while
+ * region_len // 2 < 14 000 and 2 000 above (:774).  region_len // 4 reaches 6 999 just below region_len = 28 000, so a
+ * flank reaches 4 000 + 6 999 = 10 999 bases - a region of 8 576 .. 27 999 bases beside 4 000-base scans has flanks above
+ * JG_ALIGN_MAX.  JG_ALIGN_LONG_MAX = 24 rows x 512 threads covers every flank that rule can produce.
+ * Arguments, job record and result row are jg_align_pairs's; q_len and r_len are independent, each
+ * 1 .. JG_ALIGN_LONG_MAX.  A job whose two lengths are both at most JG_ALIGN_MAX runs on the kernels jg_align_pairs runs
+ * it on and gets the same row; one call may mix both kinds, results come back in call order.  Synchronous; n_jobs == 0
+ * returns at once without touching the device.  JG_ERR_UNSUPPORTED for a length outside 1 .. JG_ALIGN_LONG_MAX (the
+ * message names the job and both lengths), JG_ERR_INVALID for a span outside n_bases - both before any launch. */
+#define JG_ALIGN_LONG_MAX 12288
+int jg_align_pairs_long(jg_engine *e, const uint8_t *bases, int64_t n_bases, int bases_loc, const void *jobs,
+                        int64_t n_jobs, int32_t *results);
+
 #ifdef __cplusplus
 }
 #endif

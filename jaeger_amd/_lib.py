@@ -18,6 +18,7 @@ JG_PTR_HOST, JG_PTR_DEVICE = 0, 1
 JG_BUF_NONE, JG_BUF_IDS = -1, -2
 JG_OK, JG_ERR_INVALID, JG_ERR_HIP, JG_ERR_UNSUPPORTED, JG_ERR_NOMEM, JG_ERR_IO = 0, -1, -2, -3, -4, -5   # jg_status
 JG_ALIGN_MAX, JG_ALIGN_REVCOMP = 6144, 1         # jg_align_pairs: longest span of a job; the job flag
+JG_ALIGN_LONG_MAX = 12288                        # jg_align_pairs_long: longest span of a job (24 rows x 512 threads)
 JG_OPT_STREAM_BYTES = 1
 JG_OPT_CONV_PC = 2
 JG_OPT_TERMINI_EXACT = 3
@@ -149,6 +150,7 @@ SYMBOLS = {
     "jg_box_calibrate": (C.c_int, [_vp, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),
     "jg_terminal_repeats": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int32, _vp]),
     "jg_align_pairs": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, _vp]),
+    "jg_align_pairs_long": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, _vp]),
     "jg_viterbi_decode": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int64, _vp, _vp]),
     "jg_dust_mask": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "jg_engine_set_dust": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32]),

@@ -1,7 +1,8 @@
 """Att-site alignments on the GPU (``postprocess/prophages.py:800-814``: ``parasail.sw_trace_scan_16`` of the flank left of
 a prophage region against the flank right of it, direct and reverse-complemented).
 
-``jg_align_pairs`` runs every alignment of a call as one workgroup and returns, per job, the score, the four counts of the
+``jg_align_pairs`` (lengths up to 6 144) and ``jg_align_pairs_long`` (up to 12 288, every flank the report's rule can
+produce) run every alignment of a call as one workgroup and return, per job, the score, the four counts of the
 best path (columns, gaps in the query row, gaps in the reference row, identical columns) and its end cell - no traceback
 matrix leaves the device.  The report also prints the aligned strings: :func:`traceback` rebuilds them on the host inside
 the box the counts name (the alignment starts at ``end - consumed + 1`` in both sequences), with the kernel's recurrences
@@ -24,6 +25,7 @@ from . import _lib as L
 MATCH, MISMATCH, OPEN, EXT = 2, -100, 100, 5
 NEG = -10 ** 8
 ALIGN_MAX = L.JG_ALIGN_MAX
+ALIGN_LONG_MAX = L.JG_ALIGN_LONG_MAX
 REVCOMP = L.JG_ALIGN_REVCOMP
 
 #: one job of ``jg_align_pairs`` (32 bytes): spans of the base buffer, bit 0 of ``flags`` = reverse-complemented reference
@@ -50,18 +52,42 @@ def make_jobs(rows) -> np.ndarray:
     return jobs
 
 
-def align_pairs(device, bases, jobs) -> np.ndarray:
-    """(n, 8) int32 from ``jg_align_pairs``: score, columns, query-row gaps, reference-row gaps, identities, end in the
-    query, end in the reference, 0.  ``bases``: uint8 array or bytes; ``jobs``: :data:`JOB_DTYPE` records."""
+def _device_call(entry: str, device, bases, jobs) -> np.ndarray:
+    """One call of the C-ABI entry point ``entry`` (``jg_align_pairs`` or ``jg_align_pairs_long``: same arguments)."""
     jobs = np.ascontiguousarray(jobs, JOB_DTYPE)
     if not isinstance(bases, np.ndarray):
         bases = np.frombuffer(bases, np.uint8)
     bases = np.ascontiguousarray(bases, np.uint8)
     res = np.zeros((max(len(jobs), 1), 8), np.int32)
     ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    L.check(device.lib.jg_align_pairs(device.handle, ptr(bases), bases.size, L.JG_PTR_HOST, ptr(jobs), len(jobs), ptr(res)),
-            "jg_align_pairs")
+    L.check(getattr(device.lib, entry)(device.handle, ptr(bases), bases.size, L.JG_PTR_HOST, ptr(jobs), len(jobs), ptr(res)),
+            entry)
     return res[:len(jobs)]
+
+
+def align_pairs(device, bases, jobs) -> np.ndarray:
+    """(n, 8) int32 from ``jg_align_pairs``: score, columns, query-row gaps, reference-row gaps, identities, end in the
+    query, end in the reference, 0.  ``bases``: uint8 array or bytes; ``jobs``: :data:`JOB_DTYPE` records, each length
+    1 .. :data:`ALIGN_MAX`."""
+    return _device_call("jg_align_pairs", device, bases, jobs)
+
+
+def align_pairs_long(device, bases, jobs) -> np.ndarray:
+    """:func:`align_pairs` over ``jg_align_pairs_long``: each length 1 .. :data:`ALIGN_LONG_MAX`; a job whose two lengths are
+    both at most :data:`ALIGN_MAX` gets the row :func:`align_pairs` returns."""
+    return _device_call("jg_align_pairs_long", device, bases, jobs)
+
+
+def align_flanks(device, bases, jobs) -> np.ndarray:
+    """The report's device call, ONE call either way: all jobs through :func:`align_pairs` when no length exceeds
+    :data:`ALIGN_MAX`, else all jobs through :func:`align_pairs_long`.  Both names are resolved in this module when the call
+    is made (a test that replaces either still sees it); no job, no call."""
+    jobs = np.ascontiguousarray(jobs, JOB_DTYPE)
+    if len(jobs) == 0:
+        return np.zeros((0, 8), np.int32)
+    if max(int(jobs["q_len"].max()), int(jobs["r_len"].max())) > ALIGN_MAX:
+        return align_pairs_long(device, bases, jobs)
+    return align_pairs(device, bases, jobs)
 
 
 def _codes(seq: str) -> np.ndarray:

@@ -1,10 +1,11 @@
-// Smith-Waterman systolic wavefront, the device core of termini_kernel (jg_termini.hip) and align_kernel<R>
+// Smith-Waterman systolic wavefront, the device core of termini_kernel (jg_termini.hip) and align_kernel<R, T, REF>
 // (jg_alignpairs.hip): local alignment of an n-row query against an m-column reference, match +2 / mismatch -100, a gap
 // of k costs 100 + 5(k-1); letters compare case-insensitively and only A/C/G/T match (parasail.matrix_create("ACGT", 2,
 // -100)).  No traceback matrix: every state carries counts of its best path (a count policy, below), and the counts of the
 // best cell are the answer.
 //
-// One workgroup of SW_T threads per job.  Thread t owns the query rows [t R, (t + 1) R) and walks its strip column by column
+// One workgroup of T threads per job (T: a template parameter of everything below that depends on it - termini_kernel runs
+// 256, align_kernel 256 or 512).  Thread t owns the query rows [t R, (t + 1) R) and walks its strip column by column
 // one step behind thread t - 1: the only values that cross threads are the H / F states of each strip's last row,
 // double-buffered in LDS, one barrier per step; threads without rows stay idle, m + n_active - 1 steps.
 // Ties - the contract with parasail's traceback, written once here: H prefers the diagonal, then the gap in the query row
@@ -15,7 +16,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-constexpr int SW_T = 256;           // threads per job
 constexpr int NEG = -1000000;       // "minus infinity" that survives a few subtractions
 constexpr int S_MATCH = 2, S_MISMATCH = -100, G_OPEN = 100, G_EXT = 5;
 
@@ -31,8 +31,9 @@ __device__ __forceinline__ int base_code(uint8_t c) {   // A,C,G,T -> 0..3 (any 
 
 // ref[j], j < m, = the code of bases[r_off + j], or with rev that of complement(bases[r_off + m - 1 - j]); the caller's next
 // barrier publishes it (sw_wavefront has one in front of its first step)
+template <int T>
 __device__ __forceinline__ void sw_load_ref(uint8_t *ref, const uint8_t *__restrict__ bases, int64_t r_off, int m, bool rev) {
-  for (int j = threadIdx.x; j < m; j += SW_T) {
+  for (int j = threadIdx.x; j < m; j += T) {
     int c = rev ? base_code(bases[r_off + m - 1 - j]) : base_code(bases[r_off + j]);
     if (rev && c < 4) c = 3 - c;                                     // A<->T, C<->G on ACGT = 0..3
     ref[j] = (uint8_t)c;
@@ -41,7 +42,7 @@ __device__ __forceinline__ void sw_load_ref(uint8_t *ref, const uint8_t *__restr
 
 // ---- count policies: what a state's best path carries besides its score ---------------------------------------------
 // A strip edge is the (H, H counts, F, F counts) of a strip's last row at one column: EDGE_PLANES int4 per thread and
-// buffer, plane p of slot s at edge[p * 2 * SW_T + s].
+// buffer, plane p of slot s at edge[p * 2 * T + s].
 
 // columns << 16 | gaps in the query row (the largest is 2 * 4 096)
 struct Counts2 {
@@ -51,16 +52,19 @@ struct Counts2 {
   __device__ __forceinline__ Counts2 query_gap() const { return {a + ((1 << 16) | 1)}; }   // one more column + query-row gap
   __device__ __forceinline__ Counts2 ref_gap() const { return {a + (1 << 16)}; }           // one more column + reference-row gap
   __device__ __forceinline__ Counts2 diagonal(bool) const { return {a + (1 << 16)}; }
+  template <int T>
   static __device__ __forceinline__ void put(int4 *edge, int slot, int h, Counts2 hc, int f, Counts2 fc) {
     edge[slot] = make_int4(h, hc.a, f, fc.a);
   }
+  template <int T>
   static __device__ __forceinline__ void get(const int4 *edge, int slot, int &h, Counts2 &hc, int &f, Counts2 &fc) {
     const int4 e = edge[slot];
     h = e.x; hc.a = e.y; f = e.z; fc.a = e.w;
   }
 };
 
-// four 16-bit fields of two ints (the largest is q_len + r_len = 12 288): a0 = columns << 16 | gaps in the query row,
+// four 16-bit fields of two ints (the largest is q_len + r_len = 24 576, columns of a 12 288 x 12 288 job; a0 stays below
+// 2^31): a0 = columns << 16 | gaps in the query row,
 // a1 = gaps in the reference row << 16 | identical columns
 struct alignas(8) Counts4 {
   int a0, a1;
@@ -69,12 +73,14 @@ struct alignas(8) Counts4 {
   __device__ __forceinline__ Counts4 query_gap() const { return {a0 + ((1 << 16) | 1), a1}; }
   __device__ __forceinline__ Counts4 ref_gap() const { return {a0 + (1 << 16), a1 + (1 << 16)}; }
   __device__ __forceinline__ Counts4 diagonal(bool same) const { return {a0 + (1 << 16), a1 + (same ? 1 : 0)}; }
+  template <int T>
   static __device__ __forceinline__ void put(int4 *edge, int slot, int h, Counts4 hc, int f, Counts4 fc) {
     edge[slot] = make_int4(h, hc.a0, hc.a1, 0);
-    edge[2 * SW_T + slot] = make_int4(f, fc.a0, fc.a1, 0);
+    edge[2 * T + slot] = make_int4(f, fc.a0, fc.a1, 0);
   }
+  template <int T>
   static __device__ __forceinline__ void get(const int4 *edge, int slot, int &h, Counts4 &hc, int &f, Counts4 &fc) {
-    const int4 eh = edge[slot], ef = edge[2 * SW_T + slot];
+    const int4 eh = edge[slot], ef = edge[2 * T + slot];
     h = eh.x; hc.a0 = eh.y; hc.a1 = eh.z;
     f = ef.x; fc.a0 = ef.y; fc.a1 = ef.z;
   }
@@ -89,8 +95,8 @@ struct SwBest {      // a best cell: score 0 = none (counts zero, i = j = -1)
 
 // ---- the wavefront --------------------------------------------------------------------------------------------------------
 // The thread's best cell of the n x m job query = bases[q_off ..], ref = the m codes sw_load_ref wrote; R <= RMAX rows
-// per thread, SW_T * R >= n; edge: EDGE_PLANES * 2 * SW_T int4 of LDS.  Ends behind a barrier.
-template <int RMAX, class Counts>
+// per thread, T * R >= n; edge: EDGE_PLANES * 2 * T int4 of LDS.  Ends behind a barrier.
+template <int T, int RMAX, class Counts>
 __device__ __forceinline__ SwBest<Counts> sw_wavefront(const uint8_t *__restrict__ bases, int64_t q_off, int n, int m, int R,
                                                        const uint8_t *ref, int4 *edge) {
   const int tid = threadIdx.x;
@@ -103,20 +109,20 @@ __device__ __forceinline__ SwBest<Counts> sw_wavefront(const uint8_t *__restrict
     q[r] = (r < R && i < n) ? base_code(bases[q_off + i]) : 5;       // 5: row does not exist
     hl[r] = 0; hlc[r] = Counts::zero(); el[r] = NEG; elc[r] = Counts::zero();
   }
-  Counts::put(edge, tid, 0, Counts::zero(), NEG, Counts::zero());
-  Counts::put(edge, SW_T + tid, 0, Counts::zero(), NEG, Counts::zero());
+  Counts::template put<T>(edge, tid, 0, Counts::zero(), NEG, Counts::zero());
+  Counts::template put<T>(edge, T + tid, 0, Counts::zero(), NEG, Counts::zero());
   SwBest<Counts> best{0, Counts::zero(), -1, -1};
   int prev_up_h = 0;                                                 // H[i0-1][j-1]
   Counts prev_up_c = Counts::zero();
   __syncthreads();
-  const int n_active = (n + R - 1) / R;                              // threads that own rows (<= SW_T)
+  const int n_active = (n + R - 1) / R;                              // threads that own rows (<= T)
   const int steps = m + n_active - 1;
   for (int step = 0; step < steps; ++step) {
     const int j = step - tid;
     int up_h = 0, up_f = NEG;
     Counts up_c = Counts::zero(), up_fc = Counts::zero();
     if (tid < n_active && j >= 0 && j < m) {
-      if (tid > 0) Counts::get(edge, ((step + 1) & 1) * SW_T + tid - 1, up_h, up_c, up_f, up_fc);   // written at step - 1
+      if (tid > 0) Counts::template get<T>(edge, ((step + 1) & 1) * T + tid - 1, up_h, up_c, up_f, up_fc);   // written at step - 1
       int dg_h = prev_up_h;
       Counts dg_c = prev_up_c;
       prev_up_h = up_h; prev_up_c = up_c;
@@ -149,21 +155,22 @@ __device__ __forceinline__ SwBest<Counts> sw_wavefront(const uint8_t *__restrict
         }
       }
     }
-    Counts::put(edge, (step & 1) * SW_T + tid, up_h, up_c, up_f, up_fc);
+    Counts::template put<T>(edge, (step & 1) * T + tid, up_h, up_c, up_f, up_fc);
     __syncthreads();
   }
   return best;
 }
 
 // ---- the best cell of the job: max score, then smallest column, then smallest row --------------------------------------
-// Tree reduction over the workgroup's SwBest (redk, redc: SW_T entries of LDS each); the job's best cell, valid in thread 0.
-template <class Counts>
+// Tree reduction over the workgroup's SwBest (redk, redc: T entries of LDS each); the job's best cell, valid in thread 0.
+// The key's 20-bit row and column fields hold the largest index of either wrapper, 12 287, with room to spare.
+template <int T, class Counts>
 __device__ __forceinline__ SwBest<Counts> sw_reduce_best(const SwBest<Counts> &mine, long long *redk, Counts *redc) {
   const int tid = threadIdx.x;
   redk[tid] = mine.score > 0 ? (((long long)mine.score << 40) | ((long long)(0xFFFFF - mine.j) << 20) | (long long)(0xFFFFF - mine.i)) : 0;
   redc[tid] = mine.counts;
   __syncthreads();
-  for (int s = SW_T / 2; s > 0; s >>= 1) {
+  for (int s = T / 2; s > 0; s >>= 1) {
     if (tid < s && redk[tid + s] > redk[tid]) { redk[tid] = redk[tid + s]; redc[tid] = redc[tid + s]; }
     __syncthreads();
   }

@@ -16,7 +16,7 @@
 // runs every case through both).
 //
 // termini_kernel: one workgroup per (contig, DTR|ITR) job, a thin wrapper of the wavefront core of jg_swwave.h (scoring, tie
-// rules and the systolic scheme are described there; align_kernel<R> of jg_alignpairs.hip is the other wrapper): the job is
+// rules and the systolic scheme are described there; align_kernel of jg_alignpairs.hip is the other wrapper), instantiated at 256 threads: the job is
 // square (n x n), rows per thread R = ceil(n / 256) is a run-time value 1 .. 16, and every state carries two counts
 // (Counts2: columns, gaps in the query row).  LDS is dynamic and sized by the launch's longest scan.
 #include <hip/hip_runtime.h>
@@ -31,7 +31,7 @@
 
 namespace {
 
-constexpr int TT = SW_T;         // threads per job
+constexpr int TT = 256;          // threads per job
 constexpr int RMAX = 16;         // rows per thread (scan <= 4096)
 
 struct TermJob {
@@ -55,9 +55,9 @@ __global__ __launch_bounds__(TT) void termini_kernel(const uint8_t *__restrict__
   int4 *edge = reinterpret_cast<int4 *>(smem + ((n + 15) & ~15)); // [2][TT] strip edges
   long long *redk = reinterpret_cast<long long *>(edge + 2 * TT); // reduction scratch
   Counts2 *redc = reinterpret_cast<Counts2 *>(redk + TT);
-  sw_load_ref(ref, bases, job.r_off, n, job.itr != 0);
-  const SwBest<Counts2> mine = sw_wavefront<RMAX, Counts2>(bases, job.q_off, n, n, (n + TT - 1) / TT, ref, edge);
-  const SwBest<Counts2> b = sw_reduce_best(mine, redk, redc);
+  sw_load_ref<TT>(ref, bases, job.r_off, n, job.itr != 0);
+  const SwBest<Counts2> mine = sw_wavefront<TT, RMAX, Counts2>(bases, job.q_off, n, n, (n + TT - 1) / TT, ref, edge);
+  const SwBest<Counts2> b = sw_reduce_best<TT>(mine, redk, redc);
   if (threadIdx.x == 0) out[blockIdx.x] = TermOut{b.score, b.counts.a >> 16, b.counts.a & 0xffff, b.i, b.j};
 }
 

@@ -851,13 +851,13 @@ def _prophage_regions_and_report(plan: RunPlan, res: RunResult, data_full: dict,
     opened = []
 
     def align(bases, jobs):
-        from .attscan import align_pairs
+        from . import attscan
         device = res.engine.device if res.engine is not None else None
         if device is None:
             from .engine import HipDevice
             device = HipDevice(plan.local_rank)
             opened.append(device)
-        return align_pairs(device, bases, jobs)
+        return attscan.align_flanks(device, bases, jobs)      # one call: the long entry point where a flank needs it
 
     try:
         prophage_report(fsize=plan.fsize, records=records, prophage_cordinates=[with_regions[r] for r in recs],

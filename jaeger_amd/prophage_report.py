@@ -5,9 +5,10 @@ repeat are the raw window boundaries and ``raw_start`` / ``raw_end`` repeat them
 
 Per region the reference aligns the flank left of it (``scan_length`` bases outside, ``off_set`` inside) against the flank
 right of it with parasail, direct and reverse-complemented.  Here the flanks of ALL regions of ALL contigs are copied into
-one compact buffer and go through ONE ``jg_align_pairs`` call (:mod:`jaeger_amd.attscan`); the aligned strings of the
-chosen orientation are rebuilt on the host from the device's counts.  Which of several co-optimal alignments parasail
-reports is unpinned.
+one compact buffer and go through ONE device call (:func:`jaeger_amd.attscan.align_flanks`: ``jg_align_pairs`` when no
+flank exceeds 6 144 bases, else ``jg_align_pairs_long``, which takes 12 288 - a flank is at most 4 000 + 6 999 = 10 999);
+the aligned strings of the chosen orientation are rebuilt on the host from the device's counts.  Which of several
+co-optimal alignments parasail reports is unpinned.
 """
 
 from __future__ import annotations
@@ -90,7 +91,7 @@ def prophage_report(fsize: int, records, prophage_cordinates, outdir, align, str
                     min_len: int = 500_000):
     """``records``: (name, sequence as read) per contig; ``prophage_cordinates``: per contig - SAME position, contigs are
     matched by record number, not by name - ``[ranges, scores]`` of :func:`jaeger_amd.prophage_segment.segment` or None;
-    ``align(bases, jobs) -> (n, 8)``: the device call (``attscan.align_pairs`` bound to a device) - called once, over a
+    ``align(bases, jobs) -> (n, 8)``: the device call (``attscan.align_flanks`` bound to a device) - called once, over a
     buffer that holds only the flanks, and not at all when no region has two non-empty flanks.  Contigs of at most
     ``min_len`` bases are skipped (the reference's hard-coded 500 000).  Writes ``outdir / "prophages_jaeger.tsv"`` when
     there is a row and returns its path, else None."""
@@ -119,9 +120,12 @@ def prophage_report(fsize: int, records, prophage_cordinates, outdir, align, str
                                   off_set=off_set, search_start=search_start, search_end=search_end, left=left_seq,
                                   right=right_seq, job=-1)
             if left_seq and right_seq:
-                if max(len(left_seq), len(right_seq)) > attscan.ALIGN_MAX:
+                # a guard the rule above cannot reach: scan_length <= 4 000, and off_set is region_len // 4 only while
+                # region_len // 2 < 14 000, i.e. region_len <= 27 999 and off_set <= 6 999 (2 000 above) - a flank is at most
+                # 4 000 + 6 999 = 10 999 bases, ALIGN_LONG_MAX is 12 288
+                if max(len(left_seq), len(right_seq)) > attscan.ALIGN_LONG_MAX:
                     raise ValueError(f"{record[0]}: region {raw_start}..{raw_end} has flanks of {len(left_seq)} / "
-                                     f"{len(right_seq)} bases, the alignment kernel takes {attscan.ALIGN_MAX}")
+                                     f"{len(right_seq)} bases, the alignment kernels take {attscan.ALIGN_LONG_MAX}")
                 reg.job = len(jobs)
                 for seq in (left_seq, right_seq):
                     parts.append(np.frombuffer(seq.encode("latin-1", "replace"), np.uint8))
