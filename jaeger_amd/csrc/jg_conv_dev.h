@@ -1,5 +1,6 @@
 // Device helpers shared by the split-f16 convolution kernels (jg_conv_f16_impl.h: the two-workgroup kernel and its
-// variants; jg_conv_pc.hip: the producer / consumer kernel of the 128-channel k = 5 residual stacks).
+// variants; jg_conv_pc.hip: the producer / consumer kernel of the 128-channel k = 5 residual stacks; jg_resblock.hip and
+// jg_resblock64.hip: the fused residual blocks, which share the F16S item swap).
 #pragma once
 #include "jg_common.h"
 
@@ -16,6 +17,7 @@ constexpr int NT = 1;         // tiles per workgroup pass
 constexpr int A_ITERS = 5;    // 16-B activation pieces per thread per chunk (4*rows_a <= 1280)
 constexpr int W_ITERS = 2;    // 16-B weight items per thread per slice
 constexpr int W_ITEMS = 2 * 2 * HN;           // 16-B items of one weight slice (chunk, tap): 8 KB
+constexpr int LUT_WAVES = 8;  // waves of a first-layer table workgroup: two per SIMD share one table half (4 tiles per pass)
 constexpr int LUT_RS = 68;    // floats per LDS row of the first-layer table (64 + 4: rows 16 apart share banks)
 
 // GELU (tanh form) as x * sigmoid(2u), u = sqrt(2/pi)(x + 0.044715 x^3): one v_exp_f32 and
@@ -119,6 +121,52 @@ __device__ __forceinline__ float mix_rem(float v, unsigned hi2) {
   if constexpr (H == 0) asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hi2), "v"(v));
   else asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hi2), "v"(v));
   return r;
+}
+
+// Lanes i and i + 32 hold channels 0-3 / 4-7 of the same 8-channel F16S item: a v_permlane32_swap per dword turns two
+// 8-byte accesses per lane into one 16-byte access (lane half h then owns the whole item of group 2j + h).
+__device__ __forceinline__ void swap32(unsigned &lo_half_keeps, unsigned &hi_half_keeps) {
+  const auto r = __builtin_amdgcn_permlane32_swap(lo_half_keeps, hi_half_keeps, false, false);
+  lo_half_keeps = r[0];
+  hi_half_keeps = r[1];
+}
+
+// Cross-lane reduction of an accumulator block's 16 registers over a half's 32 lanes (i = lane & 31) by register
+// halving: at each step a lane keeps half of its registers and receives the partner's copy of that half (DPP within
+// rows of 16, one bpermute across rows), so 16 registers cost 16 exchanges instead of 80.  Afterwards lane i holds the
+// reduction of channel register r = 8*b2 + 4*b1 + 2*b0 + b3 (bits of i): reduced_reg().
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float v) {
+  return __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), CTRL, 0xf, 0xf, false));
+}
+template <typename Op>
+__device__ __forceinline__ float lane_reduce(int i, const float (&in)[16], Op op) {
+  const bool b2 = (i & 4) != 0, b1 = (i & 2) != 0, b0 = (i & 1) != 0, b3 = (i & 8) != 0;
+  float s8[8], s4[4], s2[2];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {        // partner i ^ 7 (row_half_mirror)
+    const float keep = b2 ? in[8 + q] : in[q], send = b2 ? in[q] : in[8 + q];
+    s8[q] = op(keep, dpp_mov<0x141>(send));
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {        // partner i ^ 2 (quad_perm [2,3,0,1])
+    const float keep = b1 ? s8[4 + q] : s8[q], send = b1 ? s8[q] : s8[4 + q];
+    s4[q] = op(keep, dpp_mov<0x4e>(send));
+  }
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {        // partner i ^ 1 (quad_perm [1,0,3,2])
+    const float keep = b0 ? s4[2 + q] : s4[q], send = b0 ? s4[q] : s4[2 + q];
+    s2[q] = op(keep, dpp_mov<0xb1>(send));
+  }
+  const float keep1 = b3 ? s2[1] : s2[0], send1 = b3 ? s2[0] : s2[1];
+  const float v = op(keep1, dpp_mov<0x128>(send1));     // partner i ^ 8 (row_ror:8)
+  return op(v, __shfl_xor(v, 16, 32));                  // partner i ^ 16
+}
+// the accumulator register whose reduction lane i holds after lane_reduce(); its channel inside the 32-channel block is
+// 8 * (r >> 2) + 4 * h + (r & 3) (MFMA C/D layout).  The callers write that sum out next to their channel base: as a
+// helper of its own, or with the base passed in, it changes the order of the kernels' address arithmetic.
+__device__ __forceinline__ int reduced_reg(int i) {
+  return 8 * (int)((i & 4) != 0) + 4 * (int)((i & 2) != 0) + 2 * (int)((i & 1) != 0) + (int)((i & 8) != 0);
 }
 
 struct Tile {

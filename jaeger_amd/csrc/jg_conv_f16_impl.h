@@ -45,7 +45,6 @@
 
 namespace {
 
-
 // -DJG_STAMP: experiment build that accumulates per-phase shader cycles of every wave
 // (wait / barrier / DMA issue / LDS+MFMA / epilogue / whole kernel) and prints them per launch.
 #ifdef JG_STAMP
@@ -59,29 +58,56 @@ static __device__ unsigned long long jg_stamp_acc[8];
 #define JG_ST_END
 #endif
 
-// Wave priority: a wave in its main loop runs at priority 2, in its epilogue at 0, so that the matrix-core
-// stream of one resident workgroup is not held up by the other's epilogue arithmetic (+1.4 % measured A/B;
-// the reverse, or raising the priority only around each step's MFMA cluster, gains less).  -DJG_PRIO=0: off.
-#ifndef JG_PRIO
-#define JG_PRIO 1
-#endif
-#ifndef JG_LUT_WAVES
-#define JG_LUT_WAVES 8  // waves of a first-layer table workgroup: 8 = two per SIMD share one table half (4 tiles per pass)
-#endif
-#ifndef JG_FASTEP
-#define JG_FASTEP 0     // 1: the hot tanh-GELU patterns run the packed-f32, store-as-you-go epilogue (bit-identical; measured 2 % slower - the epilogue is bound by store-issue stalls, not by its instruction count: DESIGN 3.1)
-#endif
-#ifndef JG_PAIRED
-#define JG_PAIRED 1     // k = 5: one barrier per two taps (+1.3 % measured A/B); 0 = one per tap
-#endif
-#define JG_PRIO_MAIN() do { if (JG_PRIO) __builtin_amdgcn_s_setprio(2); } while (0)
-#define JG_PRIO_EPI() do { if (JG_PRIO) __builtin_amdgcn_s_setprio(0); } while (0)
+// One tap t of one 16-channel chunk on the matrix cores: the MFMA tap block the paired k = 5 steps and the per-tap loop
+// of k = 7 / 9 are made of (the pipelined loop interleaves differently and has its own).  In scope where it is used:
+// Wbuf, w_frag, A (this lane's first activation fragment of the chunk's slice), rows_a, a.dil, acc, TM, TN.  Reads the
+// tap's weight fragments (ring slot t) and, two position blocks at a time, the activation fragments (rows t * dil on);
+// issues the 3 x TM x TN split-f16 MFMAs.  Weights are the MFMA A operand: accumulator rows = channels, columns =
+// positions.  mid() - the caller's DMA issue - runs between two scheduling barriers once the first half of the tap's
+// MFMAs is queued, so that its cost runs under matrix-core time (has_mid false: a tap without one).  Owns no wait and no
+// barrier: the caller has published slot t and the slice.
+// A macro, not a function: the k = 5 steps have always called this text through a lambda, the k = 7 / 9 loop has always
+// held it inline, and the compiler simplifies a function before it inlines it - every function form tried (free
+// function, arguments by value or reference, one lambda for both) left the k = 5 code as it was and changed the order
+// of the k = 7 / 9 kernels' scalar spill slots.
+#define JG_MFMA_TAP(t, mid, has_mid)                                                          \
+  do {                                                                                        \
+    const uint4 *B = Wbuf + (t) * W_ITEMS + w_frag;                                           \
+    half8 wh[TN], wl[TN];                                                                     \
+    _Pragma("unroll") for (int tn = 0; tn < TN; ++tn) {                                       \
+      const uint4 vh = B[tn * 32];                                                            \
+      const uint4 vl = B[2 * HN + tn * 32];                                                   \
+      wh[tn] = *reinterpret_cast<const half8 *>(&vh);                                         \
+      wl[tn] = *reinterpret_cast<const half8 *>(&vl);                                         \
+    }                                                                                         \
+    _Pragma("unroll") for (int tp = 0; tp < TM / 2; ++tp) { /* two position blocks at a time */ \
+      half8 xh[2], xl[2];                                                                     \
+      _Pragma("unroll") for (int tq = 0; tq < 2; ++tq) {                                      \
+        const uint4 vh = A[(tp * 2 + tq) * 32 + (t) * a.dil];                                 \
+        const uint4 vl = A[2 * rows_a + (tp * 2 + tq) * 32 + (t) * a.dil];                    \
+        xh[tq] = *reinterpret_cast<const half8 *>(&vh);                                       \
+        xl[tq] = *reinterpret_cast<const half8 *>(&vl);                                       \
+      }                                                                                       \
+      _Pragma("unroll") for (int tq = 0; tq < 2; ++tq)                                        \
+        _Pragma("unroll") for (int tn = 0; tn < TN; ++tn) {                                   \
+          f32x16 &c = acc[tp * 2 + tq][tn];                                                   \
+          c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[tn], xl[tq], c, 0, 0, 0);             \
+          c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[tn], xh[tq], c, 0, 0, 0);             \
+          c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[tn], xh[tq], c, 0, 0, 0);             \
+        }                                                                                     \
+      if (tp == 0 && (has_mid)) {                                                             \
+        __builtin_amdgcn_sched_barrier(0);                                                    \
+        mid();                                                                                \
+        __builtin_amdgcn_sched_barrier(0);                                                    \
+      }                                                                                       \
+    }                                                                                         \
+  } while (0)
 
 // LUT = true is the first-layer variant: a convolution whose input is an embedding gather is linear
 // in one-hot ids, so y[p] = sum_t T_t[id[p + t]] with T_t = E . W_t (vocab x Cout, exact f32, built
 // on the host in f64).  The matrix-core loop is replaced by LDS row lookups (k rows of 64 channels per
 // output position); the epilogue is the same code.  A workgroup owns one 64-channel half of the
-// table (k * (vocab + 1) rows, row `vocab` = zeros for padding) and its JG_LUT_WAVES (8) waves cover
+// table (k * (vocab + 1) rows, row `vocab` = zeros for padding) and its LUT_WAVES (8) waves cover
 // four 256-position tiles per pass: waves {0,1} the first, {2,3} the second, ... - two waves per SIMD
 // share the table, so one's row lookups run under the other's epilogue.  K is unused (taps come from a.k).
 // CW = channel width of the workgroup tile.  128: waves 2 x 2, 128 positions x 64 channels each, exactly 128 output
@@ -99,9 +125,9 @@ template <int K, unsigned EP, bool LUT = false, bool FLAT = false, int CW = 128,
 // K = 5 fits two workgroups per CU in LDS (<= 80 KB each): hold the register file to 256 per
 // lane so that both are really resident (without the bound hipcc takes ~340 and the second
 // workgroup of a CU only starts when the first has finished).
-__global__ __launch_bounds__(LUT ? JG_LUT_WAVES * 64 : HT) __attribute__((amdgpu_waves_per_eu(K == 5 ? 2 : 1, 2)))
+__global__ __launch_bounds__(LUT ? LUT_WAVES * 64 : HT) __attribute__((amdgpu_waves_per_eu(K == 5 ? 2 : 1, 2)))
 void conv_f16x3_kernel(ConvHArgs a) {
-  constexpr int NTHR = LUT ? JG_LUT_WAVES * 64 : HT;      // threads of this variant's workgroup
+  constexpr int NTHR = LUT ? LUT_WAVES * 64 : HT;      // threads of this variant's workgroup
   constexpr int WA = K - 2;                  // weight slices in flight ahead of the matrix cores
   constexpr bool NARROW = !LUT && (CW == 64 || CW == 32);
   constexpr bool GEN = CW != 128;            // run-time output geometry (channel base, real width, out-stride)
@@ -124,7 +150,7 @@ void conv_f16x3_kernel(ConvHArgs a) {
   // in the table variant, the two channel halves of a tile on one L2.
   int vb = (int)(blockIdx.x >> lut_sh);
   if ((vgrid & 7) == 0) vb = (vb & 7) * (vgrid >> 3) + (vb >> 3);
-  constexpr int TPER = LUT ? JG_LUT_WAVES / 2 : NT;       // tiles per pass (LUT: two waves per 256-position tile)
+  constexpr int TPER = LUT ? LUT_WAVES / 2 : NT;       // tiles per pass (LUT: two waves per 256-position tile)
   const int tsub = LUT ? (wid >> 1) : 0;
   // LDS carve (16-byte units)
   const int rows_a = HM + (K - 1) * a.dil;                 // rows of one activation slice
@@ -333,15 +359,13 @@ void conv_f16x3_kernel(ConvHArgs a) {
     load_bytes(np);
     issue_x(0, 0);
 #pragma unroll
-    for (int t = 0; t < ((K == 5 && JG_PAIRED) ? 4 : WA); ++t) issue_w(0, t);
+    for (int t = 0; t < (K == 5 ? 4 : WA); ++t) issue_w(0, t);
   }
   int xc = 0;                      // running chunk count: activation buffer parity
-#ifdef JG_VALU_PROBE
-  float probe[8];
-#pragma unroll
-  for (int q = 0; q < 8; ++q) probe[q] = (float)(lane + q);
-#endif
-  JG_PRIO_MAIN();
+  // Wave priority: a wave in its main loop runs at priority 2, in its epilogue at 0, so that the matrix-core
+  // stream of one resident workgroup is not held up by the other's epilogue arithmetic (+1.4 % measured A/B;
+  // the reverse, or raising the priority only around each step's MFMA cluster, gains less).
+  __builtin_amdgcn_s_setprio(2);
   for (int pass = 0; pass < my_pairs; ++pass) {
     if constexpr (LUT) {
 #pragma unroll
@@ -506,7 +530,7 @@ void conv_f16x3_kernel(ConvHArgs a) {
       const bool last_chunk = cc == a.cc_in - 1;
       const bool tail = last_chunk && pass == my_pairs - 1;     // nothing is issued behind this chunk
       const uint4 *A = Abuf + abuf * a_items + x_frag;
-      if constexpr (K == 5 && JG_PAIRED) {
+      if constexpr (K == 5) {
         // Paired steps: one barrier per TWO taps - (t0 t1) (t2 t3) (t4) - so a chunk costs three barriers and
         // three counted waits instead of five.  Ring slots stay one per tap; the slices of a step are issued two
         // steps ahead: (cc, t4) and the next chunk's activations at step A, the next chunk's (t0 t1) at B,
@@ -519,40 +543,7 @@ void conv_f16x3_kernel(ConvHArgs a) {
               return;
             }
           }
-          const uint4 *B = Wbuf + t * W_ITEMS + w_frag;
-          half8 wh[TN], wl[TN];
-#pragma unroll
-          for (int tn = 0; tn < TN; ++tn) {
-            const uint4 vh = B[tn * 32];
-            const uint4 vl = B[2 * HN + tn * 32];
-            wh[tn] = *reinterpret_cast<const half8 *>(&vh);
-            wl[tn] = *reinterpret_cast<const half8 *>(&vl);
-          }
-#pragma unroll
-          for (int tp = 0; tp < TM / 2; ++tp) {
-            half8 xh[2], xl[2];
-#pragma unroll
-            for (int tq = 0; tq < 2; ++tq) {
-              const uint4 vh = A[(tp * 2 + tq) * 32 + t * a.dil];
-              const uint4 vl = A[2 * rows_a + (tp * 2 + tq) * 32 + t * a.dil];
-              xh[tq] = *reinterpret_cast<const half8 *>(&vh);
-              xl[tq] = *reinterpret_cast<const half8 *>(&vl);
-            }
-#pragma unroll
-            for (int tq = 0; tq < 2; ++tq)
-#pragma unroll
-              for (int tn = 0; tn < TN; ++tn) {
-                f32x16 &c = acc[tp * 2 + tq][tn];
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[tn], xl[tq], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[tn], xh[tq], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[tn], xh[tq], c, 0, 0, 0);
-              }
-            if (tp == 0 && has_mid) {
-              __builtin_amdgcn_sched_barrier(0);
-              mid();
-              __builtin_amdgcn_sched_barrier(0);
-            }
-          }
+          JG_MFMA_TAP(t, mid, has_mid);
         };
         auto nop = []() {};
         // ---- step A: taps 0, 1 ----
@@ -596,6 +587,7 @@ void conv_f16x3_kernel(ConvHArgs a) {
         ++xc;
         continue;
       }
+      // k = 7 / 9 (k = 5 has left above): one barrier and one counted wait per tap
 #pragma unroll
       for (int t = 0; t < K; ++t) {
         // -- wait for this step's operands, publish them ---------------------------------------
@@ -625,75 +617,9 @@ void conv_f16x3_kernel(ConvHArgs a) {
         };
         if (a.dbg & 2) issue_step();
         JG_ST(2);
-        // -- matrix-core work: one tap of one 16-channel chunk ----------------------------------
+        // -- matrix-core work: one tap of one 16-channel chunk, the DMA issue after its first half --
         if (!(a.dbg & 2)) {
-          const uint4 *B = Wbuf + t * W_ITEMS + w_frag;
-          half8 wh[TN], wl[TN];
-#pragma unroll
-          for (int tn = 0; tn < TN; ++tn) {
-            const uint4 vh = B[tn * 32];
-            const uint4 vl = B[2 * HN + tn * 32];
-            wh[tn] = *reinterpret_cast<const half8 *>(&vh);
-            wl[tn] = *reinterpret_cast<const half8 *>(&vl);
-          }
-#pragma unroll
-          for (int tp = 0; tp < TM / 2; ++tp) {           // two position blocks at a time
-            half8 xh[2], xl[2];
-#pragma unroll
-            for (int tq = 0; tq < 2; ++tq) {
-              const uint4 vh = A[(tp * 2 + tq) * 32 + t * a.dil];
-              const uint4 vl = A[2 * rows_a + (tp * 2 + tq) * 32 + t * a.dil];
-              xh[tq] = *reinterpret_cast<const half8 *>(&vh);
-              xl[tq] = *reinterpret_cast<const half8 *>(&vl);
-            }
-#pragma unroll
-            for (int tq = 0; tq < 2; ++tq)
-#pragma unroll
-              for (int tn = 0; tn < TN; ++tn) {
-                // weights are the MFMA A operand: acc rows = channels, cols = positions
-                f32x16 &c = acc[tp * 2 + tq][tn];
-#ifdef JG_MFMA16_PROBE
-                // experiment build (timing only, results are garbage): the same operand registers and LDS
-                // reads, but every 32x32x16 MFMA replaced by two 16x16x32 ones (same MACs) on quarter slices
-                // of the accumulator block - does the chip hold a higher clock on that shape in THIS loop?
-                {
-                typedef float f32x4 __attribute__((ext_vector_type(4)));
-                const half8 *ops[3][2] = {{&wh[tn], &xl[tq]}, {&wl[tn], &xh[tq]}, {&wh[tn], &xh[tq]}};
-#pragma unroll
-                for (int m = 0; m < 3; ++m)
-#pragma unroll
-                  for (int s2 = 0; s2 < 2; ++s2) {
-                    const int q0 = 4 * (2 * (t & 1) + s2);
-                    f32x4 d = {c[q0], c[q0 + 1], c[q0 + 2], c[q0 + 3]};
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_f16(*ops[m][0], *ops[m][1], d, 0, 0, 0);
-                    c[q0] = d[0]; c[q0 + 1] = d[1]; c[q0 + 2] = d[2]; c[q0 + 3] = d[3];
-                  }
-                continue;
-                }
-#endif
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[tn], xl[tq], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[tn], xh[tq], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[tn], xh[tq], c, 0, 0, 0);
-              }
-#ifdef JG_VALU_PROBE
-            // experiment: independent VALU work next to the MFMAs of a step (does the scheduler hide it
-            // in the matrix cores' shadow?)  JG_VALU_PROBE = number of dummy FMAs per 12-MFMA group
-#pragma unroll
-            for (int q = 0; q < JG_VALU_PROBE; ++q) probe[q & 7] = fmaf(probe[q & 7], 1.0001f, 0.5f);
-#if JG_VALU_PROBE_SCHED
-#pragma unroll
-            for (int q = 0; q < 12; ++q) {
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                          // one MFMA
-              __builtin_amdgcn_sched_group_barrier(0x002, JG_VALU_PROBE / 12, 0);         // then its share of VALU
-            }
-#endif
-#endif
-            if (tp == 0) {
-              __builtin_amdgcn_sched_barrier(0);
-              issue_step();
-              __builtin_amdgcn_sched_barrier(0);
-            }
-          }
+          JG_MFMA_TAP(t, issue_step, true);
         }
       }
       ++xc;
@@ -703,218 +629,8 @@ void conv_f16x3_kernel(ConvHArgs a) {
     // ---- pass finished: fused epilogue straight from the accumulators ----------------------
     if (a.dbg & 1) {
       if (acc[0][0][0] + acc[1][TN - 1][3] + acc[TM - 1][TN - 1][7] + acc[TM - 1][0][9] == 12345.678f) a.overflow[0] = 2;
-    } else if constexpr (JG_FASTEP && TANH && !LUT && CW == 128 && EP != JG_EP_GENERIC && K == 5) {
-      // ---- the residual stacks' hot patterns (128 channels, tanh-GELU): the same expressions on packed-f32 forms ----
-      // Every instruction a wave issues besides its MFMAs costs the SIMD matrix-core time (about 6 cycles each, whichever
-      // of the two resident waves issues it - profiles/r3_pc_*), so this epilogue is written for instruction count:
-      // v_pk_* arithmetic on channel pairs (the operation sequence per element is unchanged: results are bit-identical),
-      // output positions resolved once per position block, every block converted and stored as soon as it is finished
-      // (no write-back into the accumulator tuple: no register moves), its inputs fetched two blocks ahead so that no
-      // load's wait meets a fresh store.
-      JG_PRIO_EPI();
-      constexpr bool HAS_ADD = (EP & JG_EP_ADD) != 0;
-      constexpr bool HAS_NMD = (EP & (JG_EP_NMD1 | JG_EP_NMD2)) != 0;
-      constexpr int N1 = (EP >> 1) & 3, N2 = (EP >> 6) & 3;
-      static_assert(N1 != 2 && N2 != 2, "the tanh-GELU builds carry no DyT stage");
-      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-      const Tile &tile = cur[0];
-      float vmax = 0.f;
-      bool vnan = false;
-      const unsigned L4 = 4u * (unsigned)a.L_out;
-      unsigned ob[4], om[4], olive = 0;          // per position block: hi-plane item base, mask-byte offset, "position exists"
-#pragma unroll
-      for (int tm = 0; tm < 4; ++tm) {
-        int row, p;
-        const bool live = resolve(tile, (wm * 4 + tm) * 32 + i, a.L_out, row, p);
-        const int mc = live ? p : 0;
-        if constexpr (FLAT) {
-          if (!live) row = min(max(row, 0), a.rows - 1);
-        }
-        ob[tm] = (unsigned)(((row * 8 + 4 * wn) * 4 + h) * a.L_out + mc);
-        om[tm] = (unsigned)(row * a.L_out + mc);
-        if (live) olive |= 1u << tm;
-      }
-      struct In {                                  // what a block needs from memory
-        u32x4 sh0, sh1, sl0, sl1;                  // whole shortcut items of groups h and 2 + h, hi / lo plane (separate
-        unsigned char mkb;                         // fields, not arrays: register promotion wants static indices)
-      };
-      auto fetch = [&](In &q, int b) {
-        const int tm = b & 3, tn = b >> 2;
-        q.mkb = a.mask_out != nullptr ? a.mask_out[om[tm]] : (unsigned char)1;
-        if constexpr (HAS_ADD) {
-          if (!(a.dbg & 128)) {
-            const unsigned it0 = ob[tm] + (unsigned)(2 * tn) * L4, it1 = it0 + L4;
-            q.sh0 = ld_stream(reinterpret_cast<const u32x4 *>(a.addh + it0));
-            q.sl0 = ld_stream(reinterpret_cast<const u32x4 *>(a.addh + it0 + 2u * (unsigned)a.L_out));
-            q.sh1 = ld_stream(reinterpret_cast<const u32x4 *>(a.addh + it1));
-            q.sl1 = ld_stream(reinterpret_cast<const u32x4 *>(a.addh + it1 + 2u * (unsigned)a.L_out));
-          } else {
-            q.sh0 = q.sh1 = q.sl0 = q.sl1 = u32x4{0u, 0u, 0u, 0u};
-          }
-        }
-      };
-      auto swap32 = [](unsigned &lo_half_keeps, unsigned &hi_half_keeps) {
-        const auto r = __builtin_amdgcn_permlane32_swap(lo_half_keeps, hi_half_keeps, false, false);
-        lo_half_keeps = r[0];
-        hi_half_keeps = r[1];
-      };
-#define JG_DPP(v, ctrl) __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), (ctrl), 0xf, 0xf, false))
-      auto lane_reduce = [&](const float (&in)[16], auto op) -> float {      // (see the general epilogue below)
-        const bool b2 = (i & 4) != 0, b1 = (i & 2) != 0, b0 = (i & 1) != 0, b3 = (i & 8) != 0;
-        float s8[8], s4[4], s2[2];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const float keep = b2 ? in[8 + q] : in[q], send = b2 ? in[q] : in[8 + q];
-          s8[q] = op(keep, JG_DPP(send, 0x141));
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float keep = b1 ? s8[4 + q] : s8[q], send = b1 ? s8[q] : s8[4 + q];
-          s4[q] = op(keep, JG_DPP(send, 0x4e));
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const float keep = b0 ? s4[2 + q] : s4[q], send = b0 ? s4[q] : s4[2 + q];
-          s2[q] = op(keep, JG_DPP(send, 0xb1));
-        }
-        const float keep1 = b3 ? s2[1] : s2[0], send1 = b3 ? s2[0] : s2[1];
-        const float v = op(keep1, JG_DPP(send1, 0x128));
-        return op(v, __shfl_xor(v, 16, 32));
-      };
-#undef JG_DPP
-      auto reduced_slot = [&](int tn, int &ch) -> size_t {
-        const int r = 8 * (int)((i & 4) != 0) + 4 * (int)((i & 2) != 0) + 2 * (int)((i & 1) != 0) + (int)((i & 8) != 0);
-        ch = (wn * 2 + tn) * 32 + 8 * (r >> 2) + 4 * h + (r & 3);
-        return ((size_t)tile.T * STRIPS + wm) * a.cout + ch;
-      };
-      f32x2 nmd2[8];
-      float pool_acc[16];
-      In in0, in1;                                 // (two objects, not an array: the register promotion wants static indices)
-      fetch(in0, 0);
-      fetch(in1, 1);
-      auto do_block = [&](int b, In &q) {
-        const int tm = b & 3, tn = b >> 2;
-        f32x16 &x = acc[tm][tn];
-        const bool live = ((olive >> tm) & 1u) != 0u;
-        const float mk = (live && q.mkb != 0) ? 1.f : 0.f;
-        const int nb = (wn * 2 + tn) * 32;
-        if (tm == 0) {
-          if constexpr (HAS_NMD) {
-#pragma unroll
-            for (int r = 0; r < 8; ++r) nmd2[r] = f32x2{0.f, 0.f};
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) pool_acc[r] = -INFINITY;
-        }
-        if (!(a.dbg & 32)) {
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {              // half j: channel groups 2j, 2j + 1 (accumulator registers 8j .. 8j + 7)
-            f32x2 v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = f32x2{x[8 * j + 2 * r], x[8 * j + 2 * r + 1]};
-            auto st_affine = [&](int row) {
-              const float *pr = epiL + (row * 2) * HN + nb + 4 * h + 16 * j;
-              const float4 sc0 = *reinterpret_cast<const float4 *>(pr), sc1 = *reinterpret_cast<const float4 *>(pr + 8);
-              const float4 of0 = *reinterpret_cast<const float4 *>(pr + HN), of1 = *reinterpret_cast<const float4 *>(pr + HN + 8);
-              v[0] = __builtin_elementwise_fma(v[0], f32x2{sc0.x, sc0.y}, f32x2{of0.x, of0.y});
-              v[1] = __builtin_elementwise_fma(v[1], f32x2{sc0.z, sc0.w}, f32x2{of0.z, of0.w});
-              v[2] = __builtin_elementwise_fma(v[2], f32x2{sc1.x, sc1.y}, f32x2{of1.x, of1.y});
-              v[3] = __builtin_elementwise_fma(v[3], f32x2{sc1.z, sc1.w}, f32x2{of1.z, of1.w});
-            };
-            auto st_add = [&]() {
-              // lanes i and i + 32 loaded the whole items of groups 2j and 2j + 1: one permlane32 swap per dword pair gives
-              // every lane its own four channels of both groups
-              const u32x4 qh = j == 0 ? q.sh0 : q.sh1, ql = j == 0 ? q.sl0 : q.sl1;
-              unsigned hx = qh[0], hy = qh[1], hz = qh[2], hw_ = qh[3];
-              unsigned lx = ql[0], ly = ql[1], lz = ql[2], lw_ = ql[3];
-              swap32(hx, hz); swap32(hy, hw_);
-              swap32(lx, lz); swap32(ly, lw_);
-              v[0] += f32x2{mix_sum<0>(hx, lx), mix_sum<1>(hx, lx)};
-              v[1] += f32x2{mix_sum<0>(hy, ly), mix_sum<1>(hy, ly)};
-              v[2] += f32x2{mix_sum<0>(hz, lz), mix_sum<1>(hz, lz)};
-              v[3] += f32x2{mix_sum<0>(hw_, lw_), mix_sum<1>(hw_, lw_)};
-            };
-            auto st_gelu = [&]() {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) v[r] = fast_gelu2(v[r]);
-            };
-            auto st_nmd = [&]() {
-              const f32x2 mk2 = {mk, mk};
-#pragma unroll
-              for (int r = 0; r < 4; ++r) nmd2[4 * j + r] = __builtin_elementwise_fma(v[r], mk2, nmd2[4 * j + r]);
-            };
-            st_affine(0);
-            if constexpr (EP & JG_EP_NMD1) st_nmd();
-            if constexpr (N1 == 1) st_affine(1);
-            if constexpr (HAS_ADD) st_add();
-            if constexpr (EP & JG_EP_ACT1) st_gelu();
-            if constexpr (EP & JG_EP_NMD2) st_nmd();
-            if constexpr (N2 == 1) st_affine(N1 ? 2 : 1);
-            if constexpr (EP & JG_EP_ACT2) st_gelu();
-            if (a.out_f16s) {
-              unsigned hp[4], lp[4];
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-                const half2_t hh = {(_Float16)v[r].x, (_Float16)v[r].y};
-                hp[r] = *reinterpret_cast<const unsigned *>(&hh);
-                const half2_t ll = {(_Float16)mix_rem<0>(v[r].x, hp[r]), (_Float16)mix_rem<1>(v[r].y, hp[r])};
-                lp[r] = *reinterpret_cast<const unsigned *>(&ll);
-              }
-              vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(v[0].x), fabsf(v[0].y))), fmaxf(fabsf(v[1].x), fabsf(v[1].y)));
-              vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(v[2].x), fabsf(v[2].y))), fmaxf(fabsf(v[3].x), fabsf(v[3].y)));
-              vnan = vnan || __builtin_isunordered(v[0].x, v[0].y) || __builtin_isunordered(v[1].x, v[1].y) ||
-                     __builtin_isunordered(v[2].x, v[2].y) || __builtin_isunordered(v[3].x, v[3].y);
-              swap32(hp[0], hp[2]); swap32(hp[1], hp[3]);      // -> whole item of group 2j + h
-              swap32(lp[0], lp[2]); swap32(lp[1], lp[3]);
-              if (live && !(a.dbg & 64)) {
-                uint4 *yh = reinterpret_cast<uint4 *>(a.y);
-                const unsigned it4 = ob[tm] + (unsigned)(2 * tn + j) * L4;
-                const u32x4 vhi = {hp[0], hp[1], hp[2], hp[3]}, vlo = {lp[0], lp[1], lp[2], lp[3]};
-                st_stream(vhi, reinterpret_cast<u32x4 *>(yh + it4));
-                st_stream(vlo, reinterpret_cast<u32x4 *>(yh + it4 + 2u * (unsigned)a.L_out));
-              }
-            } else if (a.pool_out != nullptr) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                pool_acc[8 * j + 2 * r] = mk != 0.f ? fmaxf(pool_acc[8 * j + 2 * r], v[r].x) : pool_acc[8 * j + 2 * r];
-                pool_acc[8 * j + 2 * r + 1] = mk != 0.f ? fmaxf(pool_acc[8 * j + 2 * r + 1], v[r].y) : pool_acc[8 * j + 2 * r + 1];
-              }
-            } else if (live && !(a.dbg & 64)) {
-              float *yf = reinterpret_cast<float *>(a.y) + (size_t)om[tm] * a.cout + nb + 4 * h + 16 * j;
-              *reinterpret_cast<float4 *>(yf) = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
-              *reinterpret_cast<float4 *>(yf + 8) = make_float4(v[2].x, v[2].y, v[3].x, v[3].y);
-            }
-          }
-        }
-        if (b + 2 < 8) fetch(q, b + 2);
-        if (tm == 3) {
-          if constexpr (HAS_NMD) {
-            float na[16];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) { na[2 * r] = nmd2[r].x; na[2 * r + 1] = nmd2[r].y; }
-            const float rv = lane_reduce(na, [](float x_, float y_) { return x_ + y_; });
-            int ch;
-            const size_t slot = reduced_slot(tn, ch);
-            if (i < 16 && tile.valid) a.nmd_out[slot] = rv;
-          }
-          if (a.pool_out != nullptr) {
-            const float rv = lane_reduce(pool_acc, [](float x_, float y_) { return fmaxf(x_, y_); });
-            int ch;
-            const size_t slot = reduced_slot(tn, ch);
-            if (i < 16 && tile.valid) a.pool_out[slot] = rv;
-          }
-        }
-      };
-#pragma unroll
-      for (int bp = 0; bp < 4; ++bp) {
-        do_block(2 * bp, in0);
-        do_block(2 * bp + 1, in1);
-      }
-      if ((!(vmax <= 65000.0f) || vnan) && a.overflow != nullptr && a.dbg == 0) atomicOr(a.overflow, 1);
-      JG_PRIO_MAIN();
     } else {
-      JG_PRIO_EPI();
+      __builtin_amdgcn_s_setprio(0);
       float vmax = 0.f;             // running max |output|: f16-range guard
       bool vnan = false;            // ... and "an output is NaN"
       float nmd_acc[16];            // per-lane NMD sums of the current channel block
@@ -924,14 +640,6 @@ void conv_f16x3_kernel(ConvHArgs a) {
       struct Pre {
         uint2 sh[4], sl[4];
         unsigned char mkb;
-      };
-      // lanes i and i+32 hold channels 0-3 / 4-7 of the same 8-channel F16S item: a
-      // v_permlane32_swap per dword turns two 8-byte accesses per lane into one 16-byte access
-      // (lane half h then owns the whole item of group 2j+h)
-      auto swap32 = [](unsigned &lo_half_keeps, unsigned &hi_half_keeps) {
-        const auto r = __builtin_amdgcn_permlane32_swap(lo_half_keeps, hi_half_keeps, false, false);
-        lo_half_keeps = r[0];
-        hi_half_keeps = r[1];
       };
       auto item4 = [&](int row, int mc, int nb, int j) -> unsigned {
         // hi-plane item of group 2j + h (uint4 units); lo plane = + 2*L_out
@@ -1313,41 +1021,14 @@ void conv_f16x3_kernel(ConvHArgs a) {
           }
         }
       };
-      // Cross-lane reduction over a half's 32 lanes by register halving: at each step a lane keeps half of
-      // its registers and receives the partner's copy of that half (DPP within rows of 16, one bpermute
-      // across rows), so 16 registers cost 16 exchanges instead of 80.  Afterwards lane i holds the
-      // reduction of channel register r = 8*b2 + 4*b1 + 2*b0 + b3 (bits of i).
-#define JG_DPP(v, ctrl) __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), (ctrl), 0xf, 0xf, false))
-      auto lane_reduce = [&](const float (&in)[16], auto op) -> float {
-        const bool b2 = (i & 4) != 0, b1 = (i & 2) != 0, b0 = (i & 1) != 0, b3 = (i & 8) != 0;
-        float s8[8], s4[4], s2[2];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {        // partner i ^ 7 (row_half_mirror)
-          const float keep = b2 ? in[8 + q] : in[q], send = b2 ? in[q] : in[8 + q];
-          s8[q] = op(keep, JG_DPP(send, 0x141));
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {        // partner i ^ 2 (quad_perm [2,3,0,1])
-          const float keep = b1 ? s8[4 + q] : s8[q], send = b1 ? s8[q] : s8[4 + q];
-          s4[q] = op(keep, JG_DPP(send, 0x4e));
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {        // partner i ^ 1 (quad_perm [1,0,3,2])
-          const float keep = b0 ? s4[2 + q] : s4[q], send = b0 ? s4[q] : s4[2 + q];
-          s2[q] = op(keep, JG_DPP(send, 0xb1));
-        }
-        const float keep1 = b3 ? s2[1] : s2[0], send1 = b3 ? s2[0] : s2[1];
-        const float v = op(keep1, JG_DPP(send1, 0x128));      // partner i ^ 8 (row_ror:8)
-        return op(v, __shfl_xor(v, 16, 32));                  // partner i ^ 16
-      };
       // where lane i's reduced channel lives, and the partial row of this wave's 128 positions
       auto reduced_slot = [&](const Tile &tile, int tn, int &ch) -> size_t {
-        const int r = 8 * (int)((i & 4) != 0) + 4 * (int)((i & 2) != 0) + 2 * (int)((i & 1) != 0) + (int)((i & 8) != 0);
+        const int r = reduced_reg(i);
         ch = ch0 + (wn * 2 + tn) * 32 + 8 * (r >> 2) + 4 * h + (r & 3);
         return ((size_t)tile.T * STRIPS + wm) * a.cout + ch;     // one partial row per wave strip (128 / 64 positions)
       };
       auto nmd_flush = [&](const Tile &tile, int tn) {
-        const float v = lane_reduce(nmd_acc, [](float x, float y) { return x + y; });
+        const float v = lane_reduce(i, nmd_acc, [](float x, float y) { return x + y; });
         int ch;
         const size_t slot = reduced_slot(tile, tn, ch);
         if (i < 16 && tile.valid && ch < a.cout) e_nmd[slot] = v;
@@ -1366,7 +1047,7 @@ void conv_f16x3_kernel(ConvHArgs a) {
         if (has_nmd) nmd_flush(cur[0], tn);
         if constexpr (EP == JG_EP_RUNTIME) {
           if (a.nmd_out2 != nullptr) {
-            const float v2 = lane_reduce(nmd_acc2, [](float x, float y) { return x + y; });
+            const float v2 = lane_reduce(i, nmd_acc2, [](float x, float y) { return x + y; });
             int ch2;
             const size_t slot2 = reduced_slot(cur[0], tn, ch2);
             if (i < 16 && cur[0].valid && ch2 < a.cout) a.nmd_out2[slot2] = v2;
@@ -1409,7 +1090,7 @@ void conv_f16x3_kernel(ConvHArgs a) {
           for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
             for (int r = 0; r < 16; ++r) pa[r] = mkv[tm] != 0.f ? fmaxf(pa[r], acc[tm][tn][r]) : pa[r];
-          const float v = lane_reduce(pa, [](float x, float y) { return fmaxf(x, y); });
+          const float v = lane_reduce(i, pa, [](float x, float y) { return fmaxf(x, y); });
           int ch;
           const size_t slot = reduced_slot(cur[0], tn, ch);
           if (i < 16 && cur[0].valid && ch < a.cout) e_pool[slot] = v;
@@ -1439,7 +1120,7 @@ void conv_f16x3_kernel(ConvHArgs a) {
         }
       }
       if ((!(vmax <= 65000.0f) || vnan) && e_overflow != nullptr && e_dbg == 0) atomicOr(e_overflow, 1);
-      JG_PRIO_MAIN();
+      __builtin_amdgcn_s_setprio(2);
     }
     if constexpr (!PIPE) zero_acc();          // (the pipelined loop starts every tile's accumulators from C = 0)
 #pragma unroll
@@ -1448,11 +1129,10 @@ void conv_f16x3_kernel(ConvHArgs a) {
     if constexpr (!LUT) load_bytes(np);   // position bytes of the pass after next
     JG_ST(4);
   }
-#ifdef JG_VALU_PROBE
-  if (probe[0] + probe[1] + probe[2] + probe[3] + probe[4] + probe[5] + probe[6] + probe[7] == 12345.678f) a.overflow[0] = 4;
-#endif
   JG_ST_END;
 }
+
+#undef JG_MFMA_TAP
 
 // the JG_MSTAT_TAP_INSTANCE code (jaeger_hip.h: JG_INST_*) of an instance of the template in this translation unit
 constexpr int64_t pack(int k, unsigned ep, bool flat, int cw, bool tanh, unsigned ep_rt) {
@@ -1522,13 +1202,13 @@ int launch_lut_e(jg_engine *e, const ConvHArgs &a, hipStream_t s, int64_t *inst)
     attr_set = true;
   }
   const int n_tiles = a.rows * a.tiles_m;
-  constexpr int tper = JG_LUT_WAVES / 2;
+  constexpr int tper = LUT_WAVES / 2;
   const int n_pairs = (n_tiles + tper - 1) / tper;
   // (tile group, channel half), one workgroup per CU; a conv of <= 64 channels has only the first half
   const int grid = a.lut_one_half ? (n_pairs < e->n_cu ? n_pairs : e->n_cu)
                                   : 2 * (n_pairs < e->n_cu / 2 ? n_pairs : e->n_cu / 2);
   if (inst != nullptr) *inst = pack(0, EP, false, CW, TANH, a.ep_rt);      // (K = 0: the table variant takes its taps at run time)
-  hipLaunchKernelGGL((conv_f16x3_kernel<0, EP, true, false, CW, TANH>), dim3((unsigned)grid), dim3(JG_LUT_WAVES * 64), (size_t)smem, s, a);
+  hipLaunchKernelGGL((conv_f16x3_kernel<0, EP, true, false, CW, TANH>), dim3((unsigned)grid), dim3(LUT_WAVES * 64), (size_t)smem, s, a);
   JG_HIP(hipGetLastError());
   return JG_OK;
 }

@@ -484,11 +484,6 @@ void conv_pc_kernel(ConvHArgs a) {
   bool vnan = false;
   f32x2 nmd2[8];                     // NMD sums of the channel block in hand (pairs of channels)
   uint4 outv[4];                     // converted outputs of the block in hand: [j][hi | lo] items, stored a step later
-  auto swap32 = [](unsigned &lo_half_keeps, unsigned &hi_half_keeps) {
-    const auto r = __builtin_amdgcn_permlane32_swap(lo_half_keeps, hi_half_keeps, false, false);
-    lo_half_keeps = r[0];
-    hi_half_keeps = r[1];
-  };
   // half j (channel groups 2j, 2j+1: accumulator registers 8j .. 8j+7) of one 32 x 32 block.  Stage-major over the four
   // channel pairs, so that the independent chains interleave; F16S outputs go to outv[2j], outv[2j+1] (hi, lo item of group
   // 2j + h), f32 outputs stay in the accumulator registers.
@@ -597,32 +592,8 @@ void conv_pc_kernel(ConvHArgs a) {
       }
     }
   };
-#define JG_DPP(v, ctrl) __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), (ctrl), 0xf, 0xf, false))
-  auto lane_reduce = [&](const float (&in)[16], auto op) -> float {
-    const bool b2 = (i & 4) != 0, b1 = (i & 2) != 0, b0 = (i & 1) != 0, b3 = (i & 8) != 0;
-    float s8[8], s4[4], s2[2];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {        // partner i ^ 7 (row_half_mirror)
-      const float keep = b2 ? in[8 + q] : in[q], send = b2 ? in[q] : in[8 + q];
-      s8[q] = op(keep, JG_DPP(send, 0x141));
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {        // partner i ^ 2 (quad_perm [2,3,0,1])
-      const float keep = b1 ? s8[4 + q] : s8[q], send = b1 ? s8[q] : s8[4 + q];
-      s4[q] = op(keep, JG_DPP(send, 0x4e));
-    }
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {        // partner i ^ 1 (quad_perm [1,0,3,2])
-      const float keep = b0 ? s4[2 + q] : s4[q], send = b0 ? s4[q] : s4[2 + q];
-      s2[q] = op(keep, JG_DPP(send, 0xb1));
-    }
-    const float keep1 = b3 ? s2[1] : s2[0], send1 = b3 ? s2[0] : s2[1];
-    const float v = op(keep1, JG_DPP(send1, 0x128));      // partner i ^ 8 (row_ror:8)
-    return op(v, __shfl_xor(v, 16, 32));                  // partner i ^ 16
-  };
-#undef JG_DPP
   auto reduced_slot = [&](const Tile &tile, int tn, int &ch) -> size_t {
-    const int r = 8 * (int)((i & 4) != 0) + 4 * (int)((i & 2) != 0) + 2 * (int)((i & 1) != 0) + (int)((i & 8) != 0);
+    const int r = reduced_reg(i);
     ch = (wn * 2 + tn) * 32 + 8 * (r >> 2) + 4 * h + (r & 3);
     return ((size_t)tile.T * 2 + wm) * a.cout + ch;        // one partial row per wave strip (128 positions)
   };
@@ -631,7 +602,7 @@ void conv_pc_kernel(ConvHArgs a) {
     float na[16];
 #pragma unroll
     for (int q = 0; q < 8; ++q) { na[2 * q] = nmd2[q].x; na[2 * q + 1] = nmd2[q].y; }
-    const float v = lane_reduce(na, [](float x, float y) { return x + y; });
+    const float v = lane_reduce(i, na, [](float x, float y) { return x + y; });
     int ch;
     const size_t slot = reduced_slot(tile, tn, ch);
     if (i < 16 && tile.valid) a.nmd_out[slot] = v;
@@ -644,7 +615,7 @@ void conv_pc_kernel(ConvHArgs a) {
     for (int r = 0; r < 16; ++r) pool_acc[r] = mk != 0.f ? fmaxf(pool_acc[r], x[r]) : pool_acc[r];
   };
   auto pool_flush = [&](const Tile &tile, int tn) {
-    const float v = lane_reduce(pool_acc, [](float x, float y) { return fmaxf(x, y); });
+    const float v = lane_reduce(i, pool_acc, [](float x, float y) { return fmaxf(x, y); });
     int ch;
     const size_t slot = reduced_slot(tile, tn, ch);
     if (i < 16 && tile.valid) a.pool_out[slot] = v;

@@ -31,11 +31,6 @@ constexpr int RB_CC = RB_C / 16;          // 16-channel chunks
 constexpr int RB_PL = RB_CC * 4;          // (chunk, plane, half) item rows per position: 8
 constexpr int RB_NB = 4;                  // 32-position blocks of the intermediate per tile: one per wave
 
-__device__ __forceinline__ void rb_swap32(unsigned &lo_half_keeps, unsigned &hi_half_keeps) {
-  const auto r = __builtin_amdgcn_permlane32_swap(lo_half_keeps, hi_half_keeps, false, false);
-  lo_half_keeps = r[0];
-  hi_half_keeps = r[1];
-}
 
 template <int RB_K>
 __global__ __launch_bounds__(256, 2) void resblock32_kernel(JgResBlockArgs a) {
@@ -175,8 +170,8 @@ __global__ __launch_bounds__(256, 2) void resblock32_kernel(JgResBlockArgs a) {
           pl[2 * gg] = *reinterpret_cast<const unsigned *>(&l01);
           pl[2 * gg + 1] = *reinterpret_cast<const unsigned *>(&l23);
         }
-        rb_swap32(ph[0], ph[2]); rb_swap32(ph[1], ph[3]);          // -> the whole 8-channel item of group 2j + hh
-        rb_swap32(pl[0], pl[2]); rb_swap32(pl[1], pl[3]);
+        swap32(ph[0], ph[2]); swap32(ph[1], ph[3]);          // -> the whole 8-channel item of group 2j + hh
+        swap32(pl[0], pl[2]); swap32(pl[1], pl[3]);
         const int G = 2 * j + hh;
         Himg[((G >> 1) * 4 + 0 + (G & 1)) * RH + 32 * wid + i] = make_uint4(ph[0], ph[1], ph[2], ph[3]);
         Himg[((G >> 1) * 4 + 2 + (G & 1)) * RH + 32 * wid + i] = make_uint4(pl[0], pl[1], pl[2], pl[3]);
@@ -262,8 +257,8 @@ __global__ __launch_bounds__(256, 2) void resblock32_kernel(JgResBlockArgs a) {
           pl[2 * gg] = *reinterpret_cast<const unsigned *>(&l01);
           pl[2 * gg + 1] = *reinterpret_cast<const unsigned *>(&l23);
         }
-        rb_swap32(ph[0], ph[2]); rb_swap32(ph[1], ph[3]);
-        rb_swap32(pl[0], pl[2]); rb_swap32(pl[1], pl[3]);
+        swap32(ph[0], ph[2]); swap32(ph[1], ph[3]);
+        swap32(pl[0], pl[2]); swap32(pl[1], pl[3]);
         if (live) {
           // group 2j + hh = item row (chunk j, half hh): 4 L items further per j
           const unsigned off = out_off + (unsigned)j * out_step;

@@ -49,11 +49,6 @@ constexpr int R6_XR = 5;                  // input images in flight: two landing
 constexpr int R6_OR = 3;                  // per-tile bits for the conv2 waves: written at step s, read at step s + 2
 constexpr int R6_DMA = 6;                 // DMA calls per conv1 wave and image at most: 16 x (64 + 32) items / 256
 
-__device__ __forceinline__ void r6_swap32(unsigned &lo_half_keeps, unsigned &hi_half_keeps) {
-  const auto r = __builtin_amdgcn_permlane32_swap(lo_half_keeps, hi_half_keeps, false, false);
-  lo_half_keeps = r[0];
-  hi_half_keeps = r[1];
-}
 // LDS traffic of this wave done, then the workgroup barrier - WITHOUT the vmcnt(0) __syncthreads() would add (the conv2
 // waves' stores drain on their own)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -246,8 +241,8 @@ __global__ __launch_bounds__(512, 1) void resblock64_kernel(JgResBlockArgs a) {
         v23 = fast_gelu2(v23) * f32x2{m1f, m1f};
         r6_split(v01, v23, ph[2 * gg], ph[2 * gg + 1], pl[2 * gg], pl[2 * gg + 1]);
       }
-      r6_swap32(ph[0], ph[2]); r6_swap32(ph[1], ph[3]);            // -> the whole 8-channel item of group 2j + hh
-      r6_swap32(pl[0], pl[2]); r6_swap32(pl[1], pl[3]);
+      swap32(ph[0], ph[2]); swap32(ph[1], ph[3]);            // -> the whole 8-channel item of group 2j + hh
+      swap32(pl[0], pl[2]); swap32(pl[1], pl[3]);
       const int Gq = 2 * j + hh, chunk = 2 * ct + (Gq >> 1);
       Himg[(chunk * 4 + 0 + (Gq & 1)) * R6_RH + 32 * blk + i] = make_uint4(ph[0], ph[1], ph[2], ph[3]);
       Himg[(chunk * 4 + 2 + (Gq & 1)) * R6_RH + 32 * blk + i] = make_uint4(pl[0], pl[1], pl[2], pl[3]);
@@ -297,8 +292,8 @@ __global__ __launch_bounds__(512, 1) void resblock64_kernel(JgResBlockArgs a) {
         vnan = vnan || __builtin_isunordered(v01.x, v01.y) || __builtin_isunordered(v23.x, v23.y);
         r6_split(v01, v23, ph[2 * gg], ph[2 * gg + 1], pl[2 * gg], pl[2 * gg + 1]);
       }
-      r6_swap32(ph[0], ph[2]); r6_swap32(ph[1], ph[3]);
-      r6_swap32(pl[0], pl[2]); r6_swap32(pl[1], pl[3]);
+      swap32(ph[0], ph[2]); swap32(ph[1], ph[3]);
+      swap32(pl[0], pl[2]); swap32(pl[1], pl[3]);
       if (live) {
         // group 2j + hh of this wave's channels = item row (chunk 2 ct + j, half hh): 4 L items further per j
         const unsigned off = out_off + (unsigned)j * out_step;
